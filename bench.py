@@ -12,10 +12,18 @@ of synthetic chunks already resident in HBM.  Prints ONE JSON line on rank 0.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Order of the default single-GPU run: the timed headline region, then the other
-GPU legs (BF16X3 / fp32 parity modes, >= 5 s of C2 training steps, the PMC
-traffic passes), and only then the CPU legs (numpy oracle as the parity
-checker, C/OpenMP and torch-CPU baselines).
+A plain run sets up, warms up, times --steps forwards and prints the line
+(``ms_per_step`` is one timed step; ``roofline`` comes from HIP events inside
+those steps).  --dump-outputs DIR also writes what the last timed forward
+returned: ``DIR/hr_chunk0.npy`` (the first hi-res chunk, fp32) and
+``DIR/hr_sample.npy`` (a fixed, seeded sample of 2**22 values of the whole
+batch), so that two builds can be compared output for output.
+
+--full adds the side legs, in this order after the headline: the other GPU
+legs (BF16X3 / fp32 parity modes, power, >= 5 s of C2 training steps, C3,
+fwd2d, C1 / C4 / C5 training, the PMC traffic passes), and only then the CPU
+legs (numpy oracle as the parity checker, C/OpenMP and torch-CPU baselines);
+with --gpus N > 1 it adds the data-parallel training and C3 legs.
 
 Other modes (``value`` is then that mode's rate):
   --mode train  one ``Sup3rGan._train_batch`` per step, data-parallel over the
@@ -925,6 +933,21 @@ def child_leg(leg_args, world, k, limit):
             'stderr_tail': p.stderr[-600:], 'cmd': leg_args}
 
 
+def dump_outputs(out, dirname, n_sample=1 << 22, seed=0):
+    """What the timed forward returned in its last step, as fp32 .npy files:
+    the first hi-res chunk in full (14.7 MB) and ``n_sample`` values of the
+    whole batch at positions drawn with a fixed seed (the whole C2 output at
+    batch 32 is 472 MB)."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    flat = out.reshape(-1)
+    idx = np.random.default_rng(seed).integers(0, flat.numel(),
+                                               min(n_sample, flat.numel()))
+    idx = torch.from_numpy(np.sort(idx)).to(out.device)
+    np.save(os.path.join(dirname, 'hr_chunk0.npy'), out[0].cpu().numpy())
+    np.save(os.path.join(dirname, 'hr_sample.npy'), flat[idx].cpu().numpy())
+
+
 # ----------------------------------------------------------------------- main
 def main():
     ap = argparse.ArgumentParser()
@@ -944,6 +967,13 @@ def main():
                          '283, 4: 327, 8: 358 chunks/s)')
     ap.add_argument('--precision', default='bf16',
                     choices=['bf16', 'f32', 'bf16x3'])
+    ap.add_argument('--full', action='store_true',
+                    help='infer: run the side legs after the headline (parity '
+                         'modes, power, training, C3, fwd2d, PMC traffic, CPU '
+                         'baselines; the --no-* options below pick among them)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='infer: write what the last timed forward returned '
+                         'to DIR/*.npy (fp32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-parity-mode', action='store_true',
                     help='skip the BF16X3 / fp32 parity-mode measurements')
@@ -967,6 +997,8 @@ def main():
     ap.add_argument('--inner-pmc', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--force-legs', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != 'infer':
+        ap.error('--dump-outputs: the headline (--mode infer) only')
     if args.inner_pmc:
         args.batch = args.batch or 32
         return inner_pmc(args)
@@ -1171,12 +1203,14 @@ def main():
     n_prof, ms = ph.profile_end()
     elapsed = max_over_ranks(elapsed)
     assert torch.isfinite(out).all().item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
-    # Multi-GPU run: the data-parallel training step (RCCL gradient SUM) and
-    # the chunk-sharded C3 executor are measured as well, each in its OWN
-    # group of child processes (same ranks, another rendezvous port) after the
-    # headline is complete — a collective that hangs or a runtime that aborts
-    # there costs that leg, never the headline line.
+    # Multi-GPU run with --full: the data-parallel training step (RCCL
+    # gradient SUM) and the chunk-sharded C3 executor are measured as well,
+    # each in its OWN group of child processes (same ranks, another rendezvous
+    # port) after the headline is complete — a collective that hangs or a
+    # runtime that aborts there costs that leg, never the headline line.
     result_holder = {}
 
     ms_per_step = elapsed / args.steps * 1e3
@@ -1238,7 +1272,8 @@ def main():
                                 int(ph.op_is_mfma(i)), ms[i]))
     result_holder['line'] = result
     if world > 1 or args.force_legs:
-        if args.precision == 'bf16' and not args.no_train:
+        if (args.full or args.force_legs) and args.precision == 'bf16' \
+                and not args.no_train:
             legs = (('train', ['--mode', 'train', '--config', 'c2', '--steps',
                                '20'], 300),
                     ('c3', ['--mode', 'c3', '--steps', '3', '--warmup', '1'],
@@ -1251,6 +1286,9 @@ def main():
                     result[name] = sub
         if rank == 0:
             print(json.dumps(result), flush=True)
+        return
+    if not args.full:
+        print(json.dumps(result))
         return
 
     single = args.precision == 'bf16'

@@ -5,9 +5,8 @@ build, the way ``/root/reference/tests/training/test_load_configs.py:17-133``
 walks it — plus what that file cannot check without an oracle: the numbers.
 
 CPU (``-m "not gpu"``):
-* every authored spec EQUALS the reference's file (only where
-  ``/root/reference`` exists; everything below runs on the shipped copies and
-  is never skipped);
+* every authored spec EQUALS the reference's file (by a digest of its JSON
+  value, stored in ``tests/golden/reference_config_digests.json``);
 * the shape contract of ``test_load_configs.py`` on every spec;
 * the fused and the unfused device plan of every spec, interpreted in float64
   (``tests/plan_interp.py``), against the layer-by-layer oracle;
@@ -23,6 +22,7 @@ an op's elements) + 3e-2 end to end, gradients 2e-2 — and the depth_to_time /
 roll kernels bit-exactly on integers.
 """
 import glob
+import hashlib
 import json
 import os
 
@@ -35,7 +35,7 @@ from tests.plan_interp import run_plan
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SURFACE = os.path.join(HERE, '..', 'sup3r_amd', 'configs', 'sup3r')
-REF_CFG = '/root/reference/sup3r/configs'
+REF_DIGESTS = os.path.join(HERE, 'golden', 'reference_config_digests.json')
 
 # rel. path -> (low-res input shape for the numeric tests, exo name or None).
 # Shapes follow test_load_configs.py's family ((1, 5, 5, 4, 2), (3, 6, 6, 8, 2),
@@ -69,6 +69,18 @@ def load_surface(rel):
         return json.load(f)
 
 
+def json_digest(value):
+    """SHA-256 of a parsed JSON value, independent of key order and layout"""
+    text = json.dumps(value, sort_keys=True, separators=(',', ':'))
+    return hashlib.sha256(text.encode()).hexdigest()
+
+
+def reference_digests():
+    """rel. path -> digest of every spec file the reference ships"""
+    with open(REF_DIGESTS) as f:
+        return json.load(f)['files']
+
+
 def _enhancements(rel):
     parts = os.path.basename(rel).replace('.json', '').split('_')
     nums = [int(p[:-1]) for p in parts if p.endswith('x')]
@@ -91,17 +103,14 @@ def test_surface_is_complete():
     assert sum('disc' in f for f in files) == 2
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG),
-                    reason='reference configs not present on this box')
 def test_authored_surface_equals_reference():
     """the authored files are the reference's spec surface, value for value,
     and the reference ships nothing else there"""
-    ref_files = sorted(os.path.relpath(p, REF_CFG) for p in
-                       glob.glob(os.path.join(REF_CFG, '*', '*.json')))
+    ref = reference_digests()
+    ref_files = sorted(ref)
     assert ref_files == sorted(CASES)
     for rel in ref_files:
-        with open(os.path.join(REF_CFG, rel)) as f:
-            assert json.load(f) == load_surface(rel), rel
+        assert json_digest(load_surface(rel)) == ref[rel], rel
 
 
 @pytest.mark.parametrize('rel', sorted(c for c in CASES if 'gen_' in c))

@@ -1,7 +1,6 @@
 """Host-logic tests (CPU): spec parser + fusion planner of sup3r_amd.spec
 against the layer-by-layer oracle, and the reference's shape contracts
 (tests/training/test_load_configs.py in the reference)."""
-import glob
 import json
 import os
 
@@ -11,9 +10,9 @@ import pytest
 from oracle.network import Network
 from sup3r_amd import spec as S
 from tests.plan_interp import run_plan
+from tests.test_ref_surface import SURFACE, json_digest, reference_digests
 
 CFG = os.path.join(os.path.dirname(__file__), '..', 'sup3r_amd', 'configs')
-REF_CFG = '/root/reference/sup3r/configs'
 
 
 def _load(name):
@@ -94,16 +93,17 @@ def test_c2_plan_is_fully_fused():
     assert layers[0].rank == 5
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG),
-                    reason='reference configs not present on this box')
 def test_reference_generator_configs_shape_contract():
     """Every generator config the reference ships parses unchanged and obeys
-    the shape contract of tests/training/test_load_configs.py:17-133."""
-    files = sorted(glob.glob(os.path.join(REF_CFG, '*', 'gen_*.json')))
+    the shape contract of tests/training/test_load_configs.py:17-133 (the
+    shipped copies, each checked against the reference file's digest)."""
+    ref = reference_digests()
+    files = sorted(rel for rel in ref if os.path.basename(rel).startswith('gen_'))
     assert len(files) >= 16
     for fp in files:
-        with open(fp) as f:
+        with open(os.path.join(SURFACE, fp)) as f:
             spec = json.load(f)
+        assert json_digest(spec) == ref[fp], fp
         layers = S.parse_layers(spec)
         s_enh = int(np.prod([L._spatial_mult for L in layers]))
         t_enh = int(np.prod([L._temporal_mult for L in layers]))

@@ -4,7 +4,7 @@ OUT=${1:-gpurun_out/r05e}
 ROOTD=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "$ROOTD/$OUT"; cd "$ROOTD"
 python -m pytest tests -m gpu -q --timeout 1200 2>&1 | grep "passed\|failed" > "$OUT/gputests.txt"
-python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 python tools/config_census.py --out "$OUT/config_census.md" > "$OUT/census.log" 2>&1
 bash tools/pmc_bench.sh "$OUT/pmc_bench" > "$OUT/pmc_bench.log" 2>&1
 bash tools/pmc_bench.sh "$OUT/pmc_fwd2d" --mode fwd2d > "$OUT/pmc_fwd2d.log" 2>&1

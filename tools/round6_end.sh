@@ -6,7 +6,7 @@ mkdir -p "$ROOTD/$OUT"; cd "$ROOTD"
 if [ -z "$2" ]; then
   python -m pytest tests -m gpu -q 2>&1 | grep "passed\|failed" > "$OUT/gputests.txt"
 fi
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 bash tools/pmc_bench.sh "$OUT/pmc_bench" > "$OUT/pmc_bench.log" 2>&1
 bash tools/pmc_bench.sh "$OUT/pmc_fwd2d" --mode fwd2d --no-executor > "$OUT/pmc_fwd2d.log" 2>&1
 # the new kernels: BF16X3 2-D trunk (+ ablations), the taps-as-columns output conv

@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/round_end}
 ROOTD=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "$ROOTD/$OUT"
 cd "$ROOTD"
-python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 python bench.py --mode c3 --steps 20 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
 for cfg in c2 c4 c4toy c1; do
   python bench.py --mode train --config $cfg --steps 20 > "$OUT/bench_train_$cfg.json" 2> "$OUT/bench_train_$cfg.err"

@@ -2,7 +2,7 @@
 OUT=gpurun_out/r03_final4
 mkdir -p $OUT
 python -m pytest tests -m gpu -q -x > $OUT/pytest_gpu.log 2>&1; tail -3 $OUT/pytest_gpu.log
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 python bench.py --mode train --config c2 --precision bf16x3 --steps 6 > $OUT/bench_train_c2_bf16x3.json 2>/dev/null
 for cfg in c2 c4 c4toy c1; do python bench.py --mode train --config $cfg --steps 20 > $OUT/bench_train_$cfg.json 2>/dev/null; done
 python bench.py --mode c3 --steps 20 > $OUT/bench_c3.json 2>/dev/null
