@@ -302,7 +302,11 @@ __device__ inline void s3_xcd_share(int64_t n, int64_t& lo, int64_t& hi, int& k,
 struct ConvIO {
   int in_bf16 = 0, out_bf16 = 0, res_bf16 = 0;
 };
-int launch_conv_generic_fwd(s3_ctx* ctx, const ConvGeom& g, const void* x,
+// the direct-family forward kernels: MFMA tail (bf16 cells in), sliding-window
+// small conv, one thread per output otherwise
+enum class GenericFwd : uint8_t { TAIL_MFMA, SMALL, DIRECT };
+GenericFwd conv_generic_fwd_variant(const ConvGeom& g, ConvIO io, bool has_res);
+int launch_conv_generic_fwd(s3_ctx* ctx, GenericFwd v, const ConvGeom& g, const void* x,
                             const float* w, const float* bias,
                             const float* res, void* y, int out_bf16,
                             int in_bf16);
@@ -331,6 +335,16 @@ bool conv_mfma_supported(const ConvGeom& g, int precision);
 size_t conv_mfma_packed_bytes(const ConvGeom& g, int precision);
 int launch_conv_mfma_pack(s3_ctx* ctx, const ConvGeom& g, int precision,
                           const float* w, void* packed);
+// the kernels of the MFMA family: halo-tile, persistent trunk (two forms),
+// logical-axes tile, and the weights-stationary 2-D forms (trunk, split-bf16,
+// few-feature output, head).  launch_conv_mfma_fwd picks with
+// conv_mfma_fwd_variant; launch_conv_mfma_fwd_as runs a choice made earlier
+// for the same geometry and dtypes (a plan's forward)
+enum class MfmaFwd : uint8_t { TILE, PERSIST, PERSIST2, GEN, WS, WS_X3, OUT, HEAD };
+MfmaFwd conv_mfma_fwd_variant(const s3_ctx* ctx, const ConvGeom& g, int precision, ConvIO io, bool has_res);
+int launch_conv_mfma_fwd_as(s3_ctx* ctx, MfmaFwd v, const ConvGeom& g, int precision,
+                            const void* x, const void* packed, const float* bias,
+                            const void* res, void* y, ConvIO io);
 int launch_conv_mfma_fwd(s3_ctx* ctx, const ConvGeom& g, int precision,
                          const void* x, const void* packed, const float* bias,
                          const void* res, void* y, ConvIO io);
@@ -344,8 +358,9 @@ ConvGeom conv_dgrad_gen_geom(const ConvGeom& g);
 bool conv_dgrad_gen_supported(const ConvGeom& g, int precision);
 size_t conv_mfma_gen_packed_bytes(const ConvGeom& g, int precision);
 int launch_conv_mfma_gen_pack(s3_ctx* ctx, const ConvGeom& g, int precision, const float* w, void* packed);
-int launch_conv_mfma_gen_fwd(s3_ctx* ctx, const ConvGeom& g, int precision, const void* x, const void* packed,
-                             const float* bias, const void* res, void* y, ConvIO io);
+MfmaFwd conv_mfma_gen_fwd_variant(const ConvGeom& g, int precision, ConvIO io, bool has_res);
+int launch_conv_mfma_gen_fwd(s3_ctx* ctx, MfmaFwd v, const ConvGeom& g, int precision, const void* x,
+                             const void* packed, const float* bias, const void* res, void* y, ConvIO io);
 // weights-stationary persistent 2-D conv for the all-bf16 64 -> 64 k trunks of
 // the spatial generators (kernels_conv2d_ws.hip); physical 2-D geometry
 bool conv2d_ws_geom_ok(const ConvGeom& g);

@@ -453,14 +453,20 @@ bool conv_small_supported(const ConvGeom& g, int in_bf16) {
   return in_bf16 ? g.Cin == 8 : (g.Cin == 8 || g.Cin == 4);
 }
 
-int launch_conv_generic_fwd(s3_ctx* ctx, const ConvGeom& g, const void* x,
+GenericFwd conv_generic_fwd_variant(const ConvGeom& g, ConvIO io, bool has_res) {
+  if (io.in_bf16 && !io.out_bf16 && !has_res && conv_tail_mfma_supported(g) && !s3_opt_has(S3O_NO_TAIL_MFMA))
+    return GenericFwd::TAIL_MFMA;
+  if (!io.out_bf16 && !has_res && conv_small_supported(g, io.in_bf16)) return GenericFwd::SMALL;
+  return GenericFwd::DIRECT;
+}
+
+int launch_conv_generic_fwd(s3_ctx* ctx, GenericFwd v, const ConvGeom& g, const void* x,
                             const float* w, const float* bias,
                             const float* res, void* y, int out_bf16,
                             int in_bf16) {
-  if (in_bf16 && !out_bf16 && !res && conv_tail_mfma_supported(g) &&
-      !s3_opt_has(S3O_NO_TAIL_MFMA))
+  if (v == GenericFwd::TAIL_MFMA)
     return launch_conv_tail_mfma(ctx, g, x, w, bias, (float*)y);
-  if (!out_bf16 && !res && conv_small_supported(g, in_bf16)) {
+  if (v == GenericFwd::SMALL) {
     constexpr int TT = 4;
     const int64_t total = (int64_t)g.N * g.O[0] * g.O[1] * ((g.O[2] + TT - 1) / TT);
     dim3 gridS((unsigned)((total + 255) / 256)), blockS(256);

@@ -305,16 +305,32 @@ int launch_conv_mfma_pack(s3_ctx* ctx, const ConvGeom& g, int precision,
   return S3_OK;
 }
 
+MfmaFwd conv_mfma_fwd_variant(const s3_ctx* ctx, const ConvGeom& g, int precision, ConvIO io, bool has_res) {
+  if (conv_mfma_is_gen(g, precision)) return conv_mfma_gen_fwd_variant(g, precision, io, has_res);
+  if (precision == S3_PREC_BF16 && !g.in_cstride) {
+    if (conv_mfma_persist2_supported(ctx, g, io, has_res)) return MfmaFwd::PERSIST2;
+    if (conv_mfma_persist_supported(ctx, g, io, has_res)) return MfmaFwd::PERSIST;
+  }
+  return MfmaFwd::TILE;
+}
+
 int launch_conv_mfma_fwd(s3_ctx* ctx, const ConvGeom& g, int precision,
                          const void* x, const void* packed, const float* bias,
                          const void* res, void* y, ConvIO io) {
-  if (conv_mfma_is_gen(g, precision))
-    return launch_conv_mfma_gen_fwd(ctx, g, precision, x, packed, bias, res, y, io);
+  return launch_conv_mfma_fwd_as(ctx, conv_mfma_fwd_variant(ctx, g, precision, io, res != nullptr), g, precision, x,
+                                 packed, bias, res, y, io);
+}
+
+int launch_conv_mfma_fwd_as(s3_ctx* ctx, MfmaFwd v, const ConvGeom& g, int precision,
+                            const void* x, const void* packed, const float* bias,
+                            const void* res, void* y, ConvIO io) {
+  if (v != MfmaFwd::TILE && v != MfmaFwd::PERSIST && v != MfmaFwd::PERSIST2)
+    return launch_conv_mfma_gen_fwd(ctx, v, g, precision, x, packed, bias, res, y, io);
+  if (v == MfmaFwd::PERSIST2)
+    return launch_conv_mfma_persist2(ctx, g, x, (const char*)packed + (size_t)((g.Cout + CT - 1) / CT) * 27 * CT * CIN * 2, bias, res, y);
+  if (v == MfmaFwd::PERSIST)
+    return launch_conv_mfma_persist(ctx, g, x, (const char*)packed + (size_t)((g.Cout + CT - 1) / CT) * 27 * CT * CIN * 2, bias, res, y);
   if (precision == S3_PREC_BF16) {
-    if (!g.in_cstride && conv_mfma_persist2_supported(ctx, g, io, res != nullptr))
-      return launch_conv_mfma_persist2(ctx, g, x, (const char*)packed + (size_t)((g.Cout + CT - 1) / CT) * 27 * CT * CIN * 2, bias, res, y);
-    if (!g.in_cstride && conv_mfma_persist_supported(ctx, g, io, res != nullptr))
-      return launch_conv_mfma_persist(ctx, g, x, (const char*)packed + (size_t)((g.Cout + CT - 1) / CT) * 27 * CT * CIN * 2, bias, res, y);
     if (g.in_rep > 1 || g.res_rep > 1) S3_FAIL(ctx, S3_ESTATE, "conv with a fused temporal repeat off the persistent kernel");
     // tile / wave configuration (SUP3R_AMD_MFMA_TILE overrides for A/B probes)
     const int tile_env = (int)s3_opt_int(S3O_MFMA_TILE, -1);

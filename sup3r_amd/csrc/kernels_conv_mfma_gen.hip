@@ -302,22 +302,34 @@ int launch_conv_mfma_gen_pack(s3_ctx* ctx, const ConvGeom& g, int precision, con
   return S3_OK;
 }
 
-int launch_conv_mfma_gen_fwd(s3_ctx* ctx, const ConvGeom& g, int precision, const void* x, const void* packed,
-                             const float* bias, const void* res, void* y, ConvIO io) {
+MfmaFwd conv_mfma_gen_fwd_variant(const ConvGeom& g, int precision, ConvIO io, bool has_res) {
+  if (out_geom(g, precision) && conv2d_out_supported(g, precision, io, has_res)) return MfmaFwd::OUT;
+  if (conv2d_ws_supported(g, precision, io, has_res)) return MfmaFwd::WS;
+  if (conv2d_ws_x3_supported(g, precision, io, has_res)) return MfmaFwd::WS_X3;
+  if (conv2d_head_supported(g, precision, io, has_res)) return MfmaFwd::HEAD;
+  return MfmaFwd::GEN;
+}
+
+int launch_conv_mfma_gen_fwd(s3_ctx* ctx, MfmaFwd v, const ConvGeom& g, int precision, const void* x,
+                             const void* packed, const float* bias, const void* res, void* y, ConvIO io) {
   GenMap m;
   if (!gen_map(g, precision, &m)) S3_FAIL(ctx, S3_ESTATE, "gen MFMA conv: launch of an unsupported geometry");
   if (io.in_bf16 && g.Cin % 8 != 0) S3_FAIL(ctx, S3_ESTATE, "gen MFMA conv: bf16 input needs C_in % 8 == 0");
-  if (out_geom(g, precision) && conv2d_out_supported(g, precision, io, res != nullptr))
-    return launch_conv2d_out(ctx, g, precision, x,
-                             (const char*)packed + out_image_offset(g, precision, gen_tile_image_bytes(g, precision, m.ka)),
-                             bias, y);
-  if (conv2d_ws_supported(g, precision, io, res != nullptr))
-    return launch_conv2d_ws(ctx, g, x, (const char*)packed + gen_tile_image_bytes(g, precision, m.ka), bias, res, y);
-  if (conv2d_ws_x3_supported(g, precision, io, res != nullptr))
-    return launch_conv2d_ws_x3(ctx, g, x, (const char*)packed + gen_tile_image_bytes(g, precision, m.ka), bias, res, y);
-  if (conv2d_head_supported(g, precision, io, res != nullptr))
-    return launch_conv2d_head(ctx, g, x, (const char*)packed + gen_tile_image_bytes(g, precision, m.ka), bias, y,
-                              precision == S3_PREC_BF16X3);
+  switch (v) {
+    case MfmaFwd::OUT:
+      return launch_conv2d_out(ctx, g, precision, x,
+                               (const char*)packed + out_image_offset(g, precision, gen_tile_image_bytes(g, precision, m.ka)),
+                               bias, y);
+    case MfmaFwd::WS:
+      return launch_conv2d_ws(ctx, g, x, (const char*)packed + gen_tile_image_bytes(g, precision, m.ka), bias, res, y);
+    case MfmaFwd::WS_X3:
+      return launch_conv2d_ws_x3(ctx, g, x, (const char*)packed + gen_tile_image_bytes(g, precision, m.ka), bias, res, y);
+    case MfmaFwd::HEAD:
+      return launch_conv2d_head(ctx, g, x, (const char*)packed + gen_tile_image_bytes(g, precision, m.ka), bias, y,
+                                precision == S3_PREC_BF16X3);
+    case MfmaFwd::GEN: break;
+    default: S3_FAIL(ctx, S3_ESTATE, "gen MFMA conv: not a kernel of the logical-axes family");
+  }
   if (g.w_cin || g.ws_only || g.res2) S3_FAIL(ctx, S3_ESTATE, "conv planned for the weights-stationary kernel launched off it");
   if (precision == S3_PREC_BF16X3) {
     if (m.ka == 1) return launch_gen_prec<S3_PREC_BF16X3, 1>(ctx, m.l, x, packed, bias, res, y, io);

@@ -43,30 +43,76 @@ struct TensorRec {
   size_t bytes() const { return (size_t)numel * (dtype ? 2 : 4); }
 };
 
+// ---- the kernels of a conv, chosen once per plan.  select_conv picks the
+// forward family and both gradient kernels before the dtypes are known, with
+// one precedence for each; resolve_fwd makes the forward concrete once they
+// are.  Every later pass, the dispatch and the reports read these choices.
+enum class Fam : uint8_t {
+  DIRECT,         // the direct kernels (conv_generic_fwd_variant)
+  MFMA,           // halo-tile / persistent / logical-axes / weights-stationary (conv_mfma_fwd_variant)
+  FEWPOS_MFMA,    // few positions: the one-launch fp32-MFMA kernels
+  FEWPOS,         // few positions: the weight-streaming slab kernels
+  GCONV,          // general gather-MFMA conv (strided / valid-padded, C_in % 32 == 0 or C_in <= 4)
+  HALO32,         // C_in = 32 stride-1 conv: LDS-halo forward (else as GCONV)
+  HALO_S2,        // C_in = 32 stride-2 valid conv: LDS-halo forward, bf16 cells in (else as GCONV)
+  TAIL_X3,        // BF16X3 plans: banded split-bf16 MFMA tail (8 -> 2, fp32 in / out)
+};
+enum class Fwd : uint8_t {
+  NONE,
+  // the MFMA family, in MfmaFwd order
+  MFMA_TILE, MFMA_PERSIST, MFMA_PERSIST2, MFMA_GEN, CONV2D_WS, CONV2D_WS_X3, CONV2D_OUT, CONV2D_HEAD,
+  FEWPOS_MFMA, FEWPOS, GCONV, HALO32, HALO_S2, TAIL_X3,
+  // the direct family, in GenericFwd order
+  TAIL_MFMA, SMALL, DIRECT,
+};
+static Fwd fwd_of(MfmaFwd v) { return (Fwd)((int)Fwd::MFMA_TILE + (int)v); }
+static Fwd fwd_of(GenericFwd v) { return (Fwd)((int)Fwd::TAIL_MFMA + (int)v); }
+static bool fwd_is_mfma(Fwd f) { return f >= Fwd::MFMA_TILE && f <= Fwd::CONV2D_HEAD; }
+static bool fwd_is_generic(Fwd f) { return f >= Fwd::TAIL_MFMA; }
+static MfmaFwd mfma_of(Fwd f) { return (MfmaFwd)((int)f - (int)Fwd::MFMA_TILE); }
+static GenericFwd generic_of(Fwd f) { return (GenericFwd)((int)f - (int)Fwd::TAIL_MFMA); }
+enum class Wgrad : uint8_t {
+  DIRECT,
+  FEWPOS_MFMA,    // one-launch fp32-MFMA kernel (fewpos convs, and the rest with few positions)
+  FEWPOS,         // slab kernel of the fewpos family
+  TAIL, C2,       // few-channel hi-res convs
+  BF16_TRUNK, F32_TRUNK,   // 64 -> C_out 'same' 3 x 3 x 3: transpose-read bf16 / fp32 MFMA
+  BF16_GEN, BF16_2D, F32_GEN,
+};
+enum class Dgrad : uint8_t {
+  DIRECT,
+  MFMA_FRAME,     // conv over the padded frame on the MFMA tile kernels, then the fold
+  MFMA_VALID,     // ... of a valid-padded conv: straight onto x's grid
+  GEN,            // ... on the logical-axes kernel (2-D nets, few time steps)
+  FEWCH,          // C_out <= 4 'same' conv: few-channel gather conv over the frame
+  CHUNKED_FRAME, CHUNKED_VALID,   // 64 -> C_out > 64: 64-channel slices of dPre
+  C2, C2_X3,      // few-channel hi-res conv: LDS halo (BF16 / BF16X3)
+  S2, S2_X3,      // stride-2 valid conv, C_out = 32: residue classes on an LDS halo
+  GCONV,          // gather-MFMA adjoint
+  FEWPOS_MFMA, FEWPOS,
+};
+static bool dgrad_is_mfma(Dgrad d) { return d >= Dgrad::MFMA_FRAME && d <= Dgrad::CHUNKED_VALID; }
+static bool dgrad_is_valid(Dgrad d) { return d == Dgrad::MFMA_VALID || d == Dgrad::CHUNKED_VALID; }
+static bool dgrad_is_chunked(Dgrad d) { return d == Dgrad::CHUNKED_FRAME || d == Dgrad::CHUNKED_VALID; }
+static bool dgrad_is_c2(Dgrad d) { return d == Dgrad::C2 || d == Dgrad::C2_X3; }
+static bool dgrad_is_s2(Dgrad d) { return d == Dgrad::S2 || d == Dgrad::S2_X3; }
+
 struct OpRec {
   s3_op_desc d;
   ConvGeom cg;
   GatherGeom gg;
-  bool mfma = false;
+  Fam fam = Fam::DIRECT;
+  Fwd fwd = Fwd::NONE;
+  Wgrad wgrad = Wgrad::DIRECT;  // (training plans)
+  Dgrad dgrad = Dgrad::DIRECT;
   ConvIO io;
   void* packed = nullptr;
   uint64_t packed_version = 0;
-  // MFMA backward (training plans)
-  bool wgrad_mfma = false, dgrad_mfma = false, wgrad_bf16 = false, wgrad_c2 = false, wgrad_bf16_gen = false, wgrad_bf16_2d = false, wgrad_tail = false;
-  bool dgrad_valid = false;    // dgrad_mfma of a valid-padded conv: no frame / fold
   bool dgrad_frame16 = false;  // the persistent kernel writes the padded frame as bf16
   bool use16 = false;          // data gradient stages the bf16 copy of dPre its mask pass leaves behind
-  bool dgrad_gen = false;      // dgrad_mfma on the logical-axes tile kernel (2-D nets, few time steps, any channels)
-  bool dgrad_c2 = false;       // few-channel hi-res conv: LDS-halo dgrad
-  bool dgrad_s2 = false;       // stride-2 valid conv, C_out = 32: residue classes on an LDS halo
   int mask_prod = -1;          // producer conv of in0 whose activation adjoint is fused into this conv's dgrad store / fold
   int in_prod = -1;            // producer conv of in0 (any number of consumers), -1: not a conv
-  bool dgrad_fewch = false;    // C_out <= 4 'same' conv: dgrad = few-channel forward conv over the frame
-  bool dgrad_chunked = false;  // 64 -> C_out > 64 'same' conv: 64-channel slices of dPre through the tile kernel
   void* dgc_wbf[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool halo32 = false;         // C_in = 32 stride-1 conv: LDS-halo forward
-  bool halo_s2 = false;        // C_in = 32 stride-2 valid conv: LDS-halo forward (bf16 cells in)
-  bool tail_x3 = false;        // BF16X3 plans: banded split-bf16 MFMA tail (8 -> 2, fp32 in / out)
   void* h32_w = nullptr;
   uint64_t h32_version = 0;
   void* dc2_w = nullptr;
@@ -81,18 +127,13 @@ struct OpRec {
   float* dg_w32 = nullptr;     // flipped / transposed fp32 filter
   void* dg_wbf = nullptr;      // its bf16 slabs (bf16 mode)
   uint64_t dg_version = 0;
-  // general gather-MFMA conv (strided / valid-padded, C_in % 32 == 0)
-  bool gconv = false, gconv_dgrad = false, wgrad_gen = false;
-  void* gc_w = nullptr;        // bf16 [tap][co][ci]
+  void* gc_w = nullptr;        // gather-MFMA conv: bf16 [tap][co][ci]
   void* gc_wt = nullptr;       // bf16 [tap][ci][co] (data gradient)
   uint64_t gc_version = 0, gct_version = 0;
-  // few-positions GEMM path
-  bool fewpos = false;
-  bool fewpos_wgrad = false;   // few positions, small filter: only the weight gradient takes the fewpos kernel
-  bool fp_mfma = false;        // the fewpos launches of this conv are the one-launch fp32-MFMA kernels
-  bool fp_wg_mfma = false;     // ... its weight gradient at least (fewpos_wgrad ops)
-  float* fp_wt = nullptr;      // [tap][co][ci] transposed filter (dgrad)
+  float* fp_wt = nullptr;      // fewpos: [tap][co][ci] transposed filter (dgrad)
   uint64_t fp_version = 0;
+  bool fewpos() const { return fam == Fam::FEWPOS_MFMA || fam == Fam::FEWPOS; }
+  bool gconv() const { return fam == Fam::GCONV || fam == Fam::HALO32 || fam == Fam::HALO_S2; }
 };
 
 struct s3_plan {
@@ -701,33 +742,174 @@ extern "C" int s3_plan_create(s3_ctx* ctx, s3_params* params,
                             precision, training, nullptr, out);
 }
 
-extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
-                                  const s3_tensor_desc* tensors, int n_tensors,
-                                  const s3_op_desc* ops, int n_ops,
-                                  const int32_t* inputs, int n_inputs,
-                                  int32_t output, int precision, int training,
-                                  const s3_plan_options* options, s3_plan** out) {
-  if (!ctx || !params || !tensors || !ops || !out) return S3_EINVAL;
-  if (output < 0 || output >= n_tensors) S3_FAIL(ctx, S3_EINVAL, "plan: bad output id");
-  S3Options plan_opt = ctx->opt;
-  if (int orc = apply_options(ctx, plan_opt, options)) return orc;
-  s3_plan* pl = new s3_plan();
-  pl->opt = plan_opt;
-  S3OptScope opt_scope(&pl->opt);
-  pl->ctx = ctx; pl->params = params; pl->precision = precision;
-  pl->training = training; pl->output = output;
-  pl->t.resize(n_tensors);
-  for (int i = 0; i < n_tensors; ++i) {
-    memcpy(pl->t[i].dims, tensors[i].dims, sizeof(int64_t) * 5);
-    pl->t[i].numel = numel5(tensors[i].dims);
-    if (pl->t[i].numel <= 0) { delete pl; S3_FAIL(ctx, S3_EINVAL, "plan: empty tensor"); }
+// ---- kernel selection of one conv (before the dtypes are known)
+static void select_conv(s3_ctx* ctx, OpRec& o, int precision, int training, bool plan_tiny) {
+  const ConvGeom& g = o.cg;
+  const s3_op_desc& d = o.d;
+  bool mfma = conv_mfma_supported(g, precision);
+  // Round 6: a trunk-geometry conv (64 -> 64 k, 3 x 3 x 3) over <= 1 024 positions in
+  // a TRAINING plan — the lo-res stack of the reference's test shapes, BASELINE
+  // configs 4 / 5: lr (N, 4, 4, 4, 2) — leaves the halo-tile family: two or four
+  // of its tiles keep two or four CUs busy (17 us forward, 17 us data gradient,
+  // 40 + 5 us for the weight gradient whose every workgroup holds the whole 27 x
+  // 64 x 64 tile), where the one-launch fewpos kernels split the work over (tap,
+  // channel block) and take ~8 us for forward and ~8 us for both gradients.
+  // (Training plans only: an inference plan's kernels do not depend on the batch.)
+  const int64_t P_out = (int64_t)g.N * g.O[0] * g.O[1] * g.O[2];
+  // (the 3-D trunk geometry only: the logical-axes kernel of 2-D nets / few time
+  // steps keeps its layers — its tests pin the selection at such sizes)
+  const bool small_trunk = training && mfma && !conv_mfma_is_gen(g, precision) && !s3_opt_has(S3O_NO_FEWPOS) &&
+                           !s3_opt_has(S3O_NO_FEWPOS_TRUNK) && precision != S3_PREC_BF16X3 &&
+                           P_out <= 1024 && conv_fewpos_supported(g) && conv_fewpos_mfma_ok(g);
+  if (small_trunk) mfma = false;
+  bool fewpos = !mfma && !s3_opt_has(S3O_NO_FEWPOS) && conv_fewpos_supported(g);
+  // bf16 plans: the weight-streaming fp32 path only for really few
+  // positions; mid-size layers go to the gather-MFMA kernels
+  // (... unless the one-launch fp32-MFMA kernels take the layer while the
+  // chip is mostly idle: no per-step filter pack, no split-K epilogue)
+  // (BF16X3 plans keep their split-bf16 gather-MFMA kernels)
+  // (training plans only: an inference plan's kernels must not change
+  // with the batch size — chunk-by-chunk and batched runs agree bit for bit)
+  const bool fp_small = training && plan_tiny && !mfma && !s3_opt_has(S3O_NO_FEWPOS) && precision != S3_PREC_BF16X3 &&
+                        conv_fewpos_mfma_small_ok(ctx, g);
+  if (fewpos && P_out >= 256 && conv_gconv_supported(g, precision) && conv_gconv_dgrad_supported(g, precision) &&
+      conv_wgrad_gen_supported(g) && !((fp_small || small_trunk) && conv_fewpos_mfma_ok(g)))
+    fewpos = false;
+  // the few-channel head / tail convs and small filters on those kernels too
+  if (mfma) o.fam = Fam::MFMA;
+  else if (fewpos) o.fam = conv_fewpos_mfma_ok(g) ? Fam::FEWPOS_MFMA : Fam::FEWPOS;
+  else if (fp_small) o.fam = Fam::FEWPOS_MFMA;
+  else if (conv_gconv_supported(g, precision))
+    o.fam = d.res < 0 && conv_halo32_supported(ctx, g, precision)   ? Fam::HALO32
+            : d.res < 0 && conv_halo_s2_supported(ctx, g, precision) ? Fam::HALO_S2
+                                                                     : Fam::GCONV;
+  else if (d.res < 0 && conv_tail_x3_supported(g, precision)) o.fam = Fam::TAIL_X3;
+  else o.fam = Fam::DIRECT;
+
+  if (!training) return;
+  const bool fp = o.fewpos();
+  const bool fp_mfma = o.fam == Fam::FEWPOS_MFMA;
+  const bool bwd = !s3_opt_has(S3O_NO_MFMA_BWD);
+  if (fp) o.wgrad = fp_mfma ? Wgrad::FEWPOS_MFMA : Wgrad::FEWPOS;
+  else if (!bwd) o.wgrad = Wgrad::DIRECT;
+  else if (conv_wgrad_tail_supported(g, precision)) o.wgrad = Wgrad::TAIL;
+  else if (conv_wgrad_c2_supported(g, precision)) o.wgrad = Wgrad::C2;
+  else if (!small_trunk && conv_wgrad_mfma_supported(g))
+    o.wgrad = conv_wgrad_bf16_supported(g, precision) ? Wgrad::BF16_TRUNK : Wgrad::F32_TRUNK;
+  else if (conv_wgrad_bf16_gen_supported(g, precision)) o.wgrad = Wgrad::BF16_GEN;
+  else if (conv_wgrad_bf16_2d_supported(g, precision)) o.wgrad = Wgrad::BF16_2D;
+  else if (conv_wgrad_gen_supported(g)) o.wgrad = Wgrad::F32_GEN;
+  // what is left would take the generic kernel (one thread per filter
+  // element walking every position: 204 us for the 1 500 positions of
+  // the C1 discriminator's first layers); with few positions the slab
+  // kernel of the fewpos family does any C_in / C_out
+  // (its input is fp32: the dtype pass demotes the input of every conv whose
+  // weight gradient does not stage bf16)
+  else if (conv_fewpos_wgrad_ok(g) && !s3_opt_has(S3O_NO_FEWPOS))
+    o.wgrad = conv_fewpos_wgrad_mfma_ok(g) ? Wgrad::FEWPOS_MFMA : Wgrad::FEWPOS;
+  else o.wgrad = Wgrad::DIRECT;
+
+  const bool bf = precision == S3_PREC_BF16, x3 = precision == S3_PREC_BF16X3;
+  const Dgrad dg_fp = fp ? (fp_mfma ? Dgrad::FEWPOS_MFMA : Dgrad::FEWPOS) : Dgrad::DIRECT;
+  bool fewch = false;
+  if ((bf || x3) && !s3_opt_has(S3O_NO_DGRAD_FEWCH) && (g.Cout == 2 || g.Cout == 4) && g.Cin % 4 == 0 &&
+      g.d2s == 1 && (int64_t)g.N * g.D[0] * g.D[1] * g.D[2] >= 4096) {
+    // hi-res tail conv (8 -> 2): its data gradient is a conv with 2 input
+    // channels — the taps-in-K few-channel kernel over the padded frame
+    fewch = true;
+    for (int q = 0; q < 3; ++q)
+      fewch = fewch && g.k[q] == 3 && g.s[q] == 1 && g.lo[q] == 1 && g.O[q] == g.D[q];
+    fewch = fewch && conv_gconv_supported(conv_dgrad_geom(g), precision);
   }
-  for (int i = 0; i < n_inputs; ++i) {
-    if (inputs[i] < 0 || inputs[i] >= n_tensors) { delete pl; S3_FAIL(ctx, S3_EINVAL, "plan: bad input id"); }
-    pl->inputs.push_back(inputs[i]);
-    pl->t[inputs[i]].is_input = true;
+  if (!bwd) o.dgrad = dg_fp;
+  else if (!small_trunk && conv_dgrad_mfma_supported(g, precision)) o.dgrad = Dgrad::MFMA_FRAME;
+  else if (fp) o.dgrad = dg_fp;
+  // (BF16X3: the split-bf16 tile kernel takes the same geometry — the
+  // discriminator's valid 32 -> 64 conv left the gather-MFMA adjoint,
+  // 2.25 -> 0.5 ms at C2 batch 8)
+  else if ((bf || (x3 && !s3_opt_has(S3O_NO_DGRAD_X3))) && conv_dgrad_mfma_valid_supported(g, precision))
+    o.dgrad = Dgrad::MFMA_VALID;
+  else if (fewch) o.dgrad = Dgrad::FEWCH;
+  else if (conv_dgrad_chunked_supported(g, precision))
+    o.dgrad = g.lo[0] == 0 ? Dgrad::CHUNKED_VALID : Dgrad::CHUNKED_FRAME;
+  // (BF16X3 plans: the split-bf16 forms of the next two kernels, round 4)
+  else if (conv_dgrad_c2_supported(g, precision) || conv_dgrad_c2_x3_supported(g, precision))
+    o.dgrad = x3 ? Dgrad::C2_X3 : Dgrad::C2;
+  else if (conv_dgrad_s2_supported(ctx, g, precision) || conv_dgrad_s2_x3_supported(ctx, g, precision))
+    o.dgrad = x3 ? Dgrad::S2_X3 : Dgrad::S2;
+  // what is left behind a REFLECT pad (2-D nets, few time steps, odd channel
+  // counts): the padded-frame correlation on the logical-axes tile kernel
+  else if (conv_dgrad_gen_supported(g, precision)) o.dgrad = Dgrad::GEN;
+  else if (conv_gconv_dgrad_supported(g, precision)) o.dgrad = Dgrad::GCONV;
+  else o.dgrad = Dgrad::DIRECT;
+  if (dgrad_is_mfma(o.dgrad))
+    o.dg = o.dgrad == Dgrad::GEN          ? conv_dgrad_gen_geom(g)
+           : dgrad_is_chunked(o.dgrad)   ? conv_dgrad_chunk_geom(g, 0)
+           : o.dgrad == Dgrad::MFMA_VALID ? conv_dgrad_valid_geom(g)
+                                          : conv_dgrad_geom(g);
+}
+
+// the forward kernel, once the dtypes (and the fused operands) of the conv are known
+static Fwd resolve_fwd(const s3_ctx* ctx, const OpRec& o, int precision) {
+  const ConvIO& io = o.io;
+  const bool res = o.d.res >= 0;
+  const bool f32_io = !io.in_bf16 && !io.out_bf16;
+  const bool gconv_io = (!io.in_bf16 || o.cg.Cin % 8 == 0) && !io.res_bf16 && (!io.out_bf16 || o.cg.Cout % 4 == 0);
+  const Fwd generic = fwd_of(conv_generic_fwd_variant(o.cg, io, res));
+  switch (o.fam) {
+    case Fam::MFMA: return fwd_of(conv_mfma_fwd_variant(ctx, o.cg, precision, io, res));
+    case Fam::HALO32: return Fwd::HALO32;
+    case Fam::HALO_S2: return io.in_bf16 ? Fwd::HALO_S2 : gconv_io ? Fwd::GCONV : generic;
+    case Fam::GCONV: return gconv_io ? Fwd::GCONV : generic;
+    case Fam::TAIL_X3: return f32_io ? Fwd::TAIL_X3 : generic;
+    case Fam::FEWPOS_MFMA: return f32_io ? Fwd::FEWPOS_MFMA : generic;
+    case Fam::FEWPOS: return f32_io ? Fwd::FEWPOS : generic;
+    case Fam::DIRECT: break;
   }
-  auto bad = [&](const char* m) { ctx->err = m; delete pl; return S3_EINVAL; };
+  return generic;
+}
+
+// the shared workspaces a conv's kernels need (sized by the plan's largest)
+struct WorkspaceSizes {
+  size_t dpre = 0, partial = 0, dxp = 0, fp = 0;
+};
+
+static void conv_workspace(const s3_ctx* ctx, const OpRec& o, int training, WorkspaceSizes& ws) {
+  const ConvGeom& g = o.cg;
+  auto grow = [](size_t& m, size_t b) { m = std::max(m, b); };
+  size_t frame = (size_t)g.N * g.Cin * sizeof(float);   // frame of a reflect data gradient
+  for (int q = 0; q < 3; ++q) frame *= (size_t)(g.D[q] + 2 * g.lo[q]);
+  if (o.fewpos()) {
+    grow(ws.fp, conv_fewpos_partial_bytes(g));
+    if (training && g.pad_mode == S3_PAD_REFLECT) grow(ws.dxp, frame);
+  }
+  grow(ws.dpre, (size_t)g.N * g.O[0] * g.O[1] * g.O[2] * g.Cout * sizeof(float));
+  grow(ws.partial, conv_generic_wgrad_partial_bytes(g));
+  if (!training) return;
+  switch (o.wgrad) {
+    case Wgrad::FEWPOS_MFMA: case Wgrad::FEWPOS: grow(ws.partial, conv_fewpos_wgrad_partial_bytes(g)); break;
+    case Wgrad::TAIL: grow(ws.partial, conv_wgrad_tail_partial_bytes(ctx, g)); break;
+    case Wgrad::C2: grow(ws.partial, conv_wgrad_c2_partial_bytes(ctx, g)); break;
+    case Wgrad::BF16_TRUNK: grow(ws.partial, conv_wgrad_bf16_partial_bytes(ctx, g)); break;
+    case Wgrad::F32_TRUNK: grow(ws.partial, conv_wgrad_mfma_partial_bytes(ctx, g)); break;
+    case Wgrad::BF16_GEN: grow(ws.partial, conv_wgrad_bf16_gen_partial_bytes(ctx, g)); break;
+    case Wgrad::BF16_2D: grow(ws.partial, conv_wgrad_bf16_2d_partial_bytes(ctx, g)); break;
+    case Wgrad::F32_GEN: grow(ws.partial, conv_wgrad_gen_partial_bytes(ctx, g)); break;
+    case Wgrad::DIRECT: break;
+  }
+  if (o.dgrad == Dgrad::GCONV && g.pad_mode == S3_PAD_REFLECT) grow(ws.dxp, frame);
+  if (dgrad_is_mfma(o.dgrad))
+    grow(ws.dxp, (size_t)o.dg.N * o.dg.O[0] * o.dg.O[1] * o.dg.O[2] * o.dg.Cout * sizeof(float));
+}
+
+// validation of the op list and the kernel choice of every conv (S3_EINVAL: the
+// message is in ctx->err)
+static int plan_select(s3_plan* pl, const s3_op_desc* ops, WorkspaceSizes& ws) {
+  s3_ctx* ctx = pl->ctx;
+  const int precision = pl->precision, training = pl->training;
+  const int n_ops = (int)pl->ops.size(), n_tensors = (int)pl->t.size();
+  const s3_params* params = pl->params;
+  auto bad = [&](const char* m) { ctx->err = m; return S3_EINVAL; };
   // a launch-bound plan: no tensor has more than 4 096 positions (the C1 / toy
   // training shapes) — every step of it is a chain of ~5 us launches, and the
   // few-channel head / tail convs go to the one-launch fewpos kernels as well
@@ -735,8 +917,6 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
   for (int i = 0; i < n_tensors; ++i)
     if (pl->t[i].numel / std::max<int64_t>(1, pl->t[i].dims[4]) > 4096) plan_tiny = false;
   const int np = (int)params->p.size();
-  pl->ops.resize(n_ops);
-  size_t max_dpre = 0, max_partial = 0, max_t = 0, max_dxp = 0, max_fp = 0;
   for (int i = 0; i < n_ops; ++i) {
     OpRec& o = pl->ops[i];
     o.d = ops[i];
@@ -764,146 +944,15 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
             return bad("plan: reflect padding exceeds the tensor extent");
         }
         if (d.res >= 0 && pl->t[d.res].numel != ot.numel) return bad("plan: residual shape mismatch");
-        o.mfma = conv_mfma_supported(g, precision);
-        // Round 6: a trunk-geometry conv (64 -> 64 k, 3 x 3 x 3) over <= 1 024 positions in
-        // a TRAINING plan — the lo-res stack of the reference's test shapes, BASELINE
-        // configs 4 / 5: lr (N, 4, 4, 4, 2) — leaves the halo-tile family: two or four
-        // of its tiles keep two or four CUs busy (17 us forward, 17 us data gradient,
-        // 40 + 5 us for the weight gradient whose every workgroup holds the whole 27 x
-        // 64 x 64 tile), where the one-launch fewpos kernels split the work over (tap,
-        // channel block) and take ~8 us for forward and ~8 us for both gradients.
-        // (Training plans only: an inference plan's kernels do not depend on the batch.)
-        const int64_t P_out = (int64_t)g.N * g.O[0] * g.O[1] * g.O[2];
-        // (the 3-D trunk geometry only: the logical-axes kernel of 2-D nets / few time
-        // steps keeps its layers — its tests pin the selection at such sizes)
-        const bool small_trunk = training && o.mfma && !conv_mfma_is_gen(g, precision) && !s3_opt_has(S3O_NO_FEWPOS) &&
-                                 !s3_opt_has(S3O_NO_FEWPOS_TRUNK) && precision != S3_PREC_BF16X3 &&
-                                 P_out <= 1024 && conv_fewpos_supported(g) && conv_fewpos_mfma_ok(g);
-        if (small_trunk) o.mfma = false;
-        o.fewpos = !o.mfma && !s3_opt_has(S3O_NO_FEWPOS) && conv_fewpos_supported(g);
-        // bf16 plans: the weight-streaming fp32 path only for really few
-        // positions; mid-size layers go to the gather-MFMA kernels
-        // (... unless the one-launch fp32-MFMA kernels take the layer while the
-        // chip is mostly idle: no per-step filter pack, no split-K epilogue)
-        // (BF16X3 plans keep their split-bf16 gather-MFMA kernels)
-        // (training plans only: an inference plan's kernels must not change
-        // with the batch size — chunk-by-chunk and batched runs agree bit for bit)
-        const bool fp_small = training && plan_tiny && !o.mfma && !s3_opt_has(S3O_NO_FEWPOS) && precision != S3_PREC_BF16X3 &&
-                              conv_fewpos_mfma_small_ok(ctx, g);
-        if (o.fewpos && (int64_t)g.N * g.O[0] * g.O[1] * g.O[2] >= 256 &&
-            conv_gconv_supported(g, precision) && conv_gconv_dgrad_supported(g, precision) &&
-            conv_wgrad_gen_supported(g) && !((fp_small || small_trunk) && conv_fewpos_mfma_ok(g)))
-          o.fewpos = false;
-        // the few-channel head / tail convs and small filters on those kernels too
-        bool fp_small_taken = false;
-        if (!o.fewpos && fp_small) { o.fewpos = true; fp_small_taken = true; }
-        o.gconv = !o.mfma && !o.fewpos && conv_gconv_supported(g, precision);
-        o.halo32 = o.gconv && d.res < 0 && conv_halo32_supported(ctx, g, precision);
-        o.halo_s2 = o.gconv && d.res < 0 && conv_halo_s2_supported(ctx, g, precision);
-        o.tail_x3 = !o.mfma && !o.fewpos && d.res < 0 && conv_tail_x3_supported(g, precision);
-        if (o.fewpos) {
-          o.fp_mfma = fp_small_taken || conv_fewpos_mfma_ok(g);
-          max_fp = std::max(max_fp, conv_fewpos_partial_bytes(g));
-          if (training) {
-            max_partial = std::max(max_partial, conv_fewpos_wgrad_partial_bytes(g));
-            if (g.pad_mode == S3_PAD_REFLECT) {   // frame of the reflect dgrad
-              size_t fb = (size_t)g.N * g.Cin * sizeof(float);
-              for (int q = 0; q < 3; ++q) fb *= (size_t)(g.D[q] + 2 * g.lo[q]);
-              max_dxp = std::max(max_dxp, fb);
-            }
-          }
-        }
-        size_t ysz = (size_t)g.N * g.O[0] * g.O[1] * g.O[2] * g.Cout * sizeof(float);
-        max_dpre = std::max(max_dpre, ysz);
-        max_partial = std::max(max_partial, conv_generic_wgrad_partial_bytes(g));
-        if (training && !s3_opt_has(S3O_NO_MFMA_BWD)) {
-          o.wgrad_mfma = !small_trunk && conv_wgrad_mfma_supported(g);
-          o.wgrad_bf16 = o.wgrad_mfma && conv_wgrad_bf16_supported(g, precision);
-          if (o.wgrad_bf16)
-            max_partial = std::max(max_partial, conv_wgrad_bf16_partial_bytes(ctx, g));
-          else if (o.wgrad_mfma)
-            max_partial = std::max(max_partial, conv_wgrad_mfma_partial_bytes(ctx, g));
-          o.wgrad_tail = !o.fewpos && conv_wgrad_tail_supported(g, precision);
-          if (o.wgrad_tail)
-            max_partial = std::max(max_partial, conv_wgrad_tail_partial_bytes(ctx, g));
-          o.wgrad_c2 = !o.fewpos && !o.wgrad_tail && conv_wgrad_c2_supported(g, precision);
-          if (o.wgrad_c2)
-            max_partial = std::max(max_partial, conv_wgrad_c2_partial_bytes(ctx, g));
-          o.wgrad_bf16_gen = !o.wgrad_mfma && !o.fewpos && !o.wgrad_c2 && !o.wgrad_tail &&
-                             conv_wgrad_bf16_gen_supported(g, precision);
-          if (o.wgrad_bf16_gen)
-            max_partial = std::max(max_partial, conv_wgrad_bf16_gen_partial_bytes(ctx, g));
-          o.wgrad_bf16_2d = !o.wgrad_mfma && !o.fewpos && !o.wgrad_c2 && !o.wgrad_tail && !o.wgrad_bf16_gen &&
-                            conv_wgrad_bf16_2d_supported(g, precision);
-          if (o.wgrad_bf16_2d)
-            max_partial = std::max(max_partial, conv_wgrad_bf16_2d_partial_bytes(ctx, g));
-          if (!o.wgrad_mfma && !o.fewpos && !o.wgrad_c2 && !o.wgrad_tail && !o.wgrad_bf16_gen && !o.wgrad_bf16_2d &&
-              conv_wgrad_gen_supported(g)) {
-            o.wgrad_gen = true;
-            max_partial = std::max(max_partial, conv_wgrad_gen_partial_bytes(ctx, g));
-          }
-          // what is left would take the generic kernel (one thread per filter
-          // element walking every position: 204 us for the 1 500 positions of
-          // the C1 discriminator's first layers); with few positions the slab
-          // kernel of the fewpos family does any C_in / C_out
-          if (!o.wgrad_mfma && !o.fewpos && !o.wgrad_c2 && !o.wgrad_tail && !o.wgrad_bf16_gen && !o.wgrad_bf16_2d &&
-              !o.wgrad_gen && conv_fewpos_wgrad_ok(g) && !s3_opt_has(S3O_NO_FEWPOS)) {
-            o.fewpos_wgrad = true;
-            o.fp_wg_mfma = conv_fewpos_wgrad_mfma_ok(g);
-            max_partial = std::max(max_partial, conv_fewpos_wgrad_partial_bytes(g));
-          }
-          o.dgrad_mfma = !small_trunk && conv_dgrad_mfma_supported(g, precision);
-          // (BF16X3: the split-bf16 tile kernel takes the same geometry — the
-          // discriminator's valid 32 -> 64 conv left the gather-MFMA adjoint,
-          // 2.25 -> 0.5 ms at C2 batch 8)
-          if (!o.dgrad_mfma && !o.fewpos &&
-              (precision == S3_PREC_BF16 || (precision == S3_PREC_BF16X3 && !s3_opt_has(S3O_NO_DGRAD_X3))) &&
-              conv_dgrad_mfma_valid_supported(g, precision)) {
-            o.dgrad_mfma = o.dgrad_valid = true;
-          }
-          if (!o.dgrad_mfma && !o.fewpos && (precision == S3_PREC_BF16 || precision == S3_PREC_BF16X3) &&
-              !s3_opt_has(S3O_NO_DGRAD_FEWCH) &&
-              (g.Cout == 2 || g.Cout == 4) && g.Cin % 4 == 0 && g.d2s == 1 &&
-              (int64_t)g.N * g.D[0] * g.D[1] * g.D[2] >= 4096) {
-            // hi-res tail conv (8 -> 2): its data gradient is a conv with 2 input
-            // channels — the taps-in-K few-channel kernel over the padded frame
-            bool same = true;
-            for (int q = 0; q < 3; ++q)
-              same = same && g.k[q] == 3 && g.s[q] == 1 && g.lo[q] == 1 && g.O[q] == g.D[q];
-            if (same && conv_gconv_supported(conv_dgrad_geom(g), precision))
-              o.dgrad_mfma = o.dgrad_fewch = true;
-          }
-          if (!o.dgrad_mfma && !o.fewpos && conv_dgrad_chunked_supported(g, precision)) {
-            o.dgrad_mfma = o.dgrad_chunked = true;
-            o.dgrad_valid = g.lo[0] == 0;
-          }
-          // (BF16X3 plans: the split-bf16 forms of the same two kernels, round 4)
-          o.dgrad_c2 = !o.dgrad_mfma && !o.fewpos &&
-                       (conv_dgrad_c2_supported(g, precision) || conv_dgrad_c2_x3_supported(g, precision));
-          o.dgrad_s2 = !o.dgrad_mfma && !o.dgrad_c2 && !o.fewpos &&
-                       (conv_dgrad_s2_supported(ctx, g, precision) || conv_dgrad_s2_x3_supported(ctx, g, precision));
-          // what is left behind a REFLECT pad (2-D nets, few time steps, odd channel
-          // counts): the padded-frame correlation on the logical-axes tile kernel
-          if (!o.dgrad_mfma && !o.dgrad_c2 && !o.dgrad_s2 && !o.fewpos && conv_dgrad_gen_supported(g, precision))
-            o.dgrad_mfma = o.dgrad_gen = true;
-          o.gconv_dgrad = !o.dgrad_mfma && !o.dgrad_c2 && !o.dgrad_s2 && !o.fewpos && conv_gconv_dgrad_supported(g, precision);
-          if (o.gconv_dgrad && g.pad_mode == S3_PAD_REFLECT)
-            max_dxp = std::max(max_dxp, (size_t)g.N * (g.D[0] + 2 * g.lo[0]) * (g.D[1] + 2 * g.lo[1]) *
-                                            (g.D[2] + 2 * g.lo[2]) * g.Cin * sizeof(float));
-          if (o.dgrad_mfma) {
-            o.dg = o.dgrad_gen ? conv_dgrad_gen_geom(g)
-                   : o.dgrad_chunked ? conv_dgrad_chunk_geom(g, 0)
-                                     : (o.dgrad_valid ? conv_dgrad_valid_geom(g) : conv_dgrad_geom(g));
-            max_dxp = std::max(max_dxp, (size_t)o.dg.N * o.dg.O[0] * o.dg.O[1] * o.dg.O[2] * o.dg.Cout * sizeof(float));
-          }
-        }
+        select_conv(ctx, o, precision, training, plan_tiny);
+        conv_workspace(ctx, o, training, ws);
       } break;
       case S3_OP_DENSE: {
         if (d.w < 0) return bad("plan: dense without weights");
         const TensorRec& it = pl->t[d.in0];
         const TensorRec& ot = pl->t[d.out];
         if (params->p[d.w].size != it.dims[4] * ot.dims[4]) return bad("plan: dense weight size mismatch");
-        max_dpre = std::max(max_dpre, (size_t)ot.numel * sizeof(float));
+        ws.dpre = std::max(ws.dpre, (size_t)ot.numel * sizeof(float));
       } break;
       case S3_OP_REPEAT_T: case S3_OP_D2S: case S3_OP_PAD: case S3_OP_CROP:
       case S3_OP_ROLL_T: case S3_OP_DILATE:
@@ -926,96 +975,109 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
         return bad("plan: unknown op kind");
     }
   }
-  // ---- inference plans: Sup3rConcat of a 64-channel tensor and ONE exogenous
-  // channel in front of a 3 x 3 Conv2D (sup3rcc/gen_wind_5x_1x_6f at hi-res: a
-  // 65-channel fp32 tensor written, read back by a two-pass fp32 conv: 28 of
-  // 126 ms at 96 x 750 x 750).  The conv is linear in its input channels: it
-  // runs as the 64 -> C_out conv over the bf16 tensor on the weights-stationary
-  // kernel, which adds the exogenous channel's nine taps per output from the
-  // fp32 field itself (ConvGeom::w_cin / exo); the concat never runs.  Checked
-  // again once the dtypes are known; if the kernel cannot take the conv after
-  // all the plan is built again without the split.
-  static thread_local int tl_no_ws_exo = 0;
-  if (!training && precision == S3_PREC_BF16 && !s3_opt_has(S3O_NO_WS_EXO) && !s3_opt_has(S3O_FP32_ACT) &&
-      !tl_no_ws_exo) {
-    for (int i = 0; i < n_ops; ++i) {
-      OpRec& c = pl->ops[i];
-      if (c.d.kind != S3_OP_CONCAT) continue;
-      const TensorRec& xt = pl->t[c.d.in0];
-      const TensorRec& et = pl->t[c.d.in1];
-      if (xt.dims[4] != 64 || et.dims[4] != 1 || !pl->t[root_of(pl, c.d.in1)].is_input) continue;
-      const int ct_ = root_of(pl, c.d.out);
-      if (ct_ == root_of(pl, output)) continue;
-      int user = -1, n_use = 0;
+  return S3_OK;
+}
+
+// ---- inference plans: Sup3rConcat of a 64-channel tensor and ONE exogenous
+// channel in front of a 3 x 3 Conv2D (sup3rcc/gen_wind_5x_1x_6f at hi-res: a
+// 65-channel fp32 tensor written, read back by a two-pass fp32 conv: 28 of
+// 126 ms at 96 x 750 x 750).  The conv is linear in its input channels: it
+// runs as the 64 -> C_out conv over the bf16 tensor on the weights-stationary
+// kernel, which adds the exogenous channel's nine taps per output from the
+// fp32 field itself (ConvGeom::w_cin / exo); the concat never runs.  Checked
+// again once the dtypes are known; if the kernel cannot take the conv after
+// all the plan is built again without the split.
+static thread_local int tl_no_ws_exo = 0;
+
+static void plan_ws_exo(s3_plan* pl) {
+  const int precision = pl->precision, training = pl->training, output = pl->output;
+  const int n_ops = (int)pl->ops.size();
+  if (training || precision != S3_PREC_BF16 || s3_opt_has(S3O_NO_WS_EXO) || s3_opt_has(S3O_FP32_ACT) || tl_no_ws_exo)
+    return;
+  for (int i = 0; i < n_ops; ++i) {
+    OpRec& c = pl->ops[i];
+    if (c.d.kind != S3_OP_CONCAT) continue;
+    const TensorRec& xt = pl->t[c.d.in0];
+    const TensorRec& et = pl->t[c.d.in1];
+    if (xt.dims[4] != 64 || et.dims[4] != 1 || !pl->t[root_of(pl, c.d.in1)].is_input) continue;
+    const int ct_ = root_of(pl, c.d.out);
+    if (ct_ == root_of(pl, output)) continue;
+    int user = -1, n_use = 0;
+    for (int k = 0; k < n_ops; ++k) {
+      const s3_op_desc& u = pl->ops[k].d;
+      for (int id : {u.in0, u.in1, u.res})
+        if (id >= 0 && root_of(pl, id) == ct_) { ++n_use; user = k; }
+    }
+    if (n_use != 1 || user <= i) continue;
+    OpRec& v = pl->ops[user];
+    if (v.d.kind != S3_OP_CONV || root_of(pl, v.d.in0) != ct_ || v.cg.Cin != 65) continue;
+    ConvGeom gs = v.cg;
+    gs.Cin = 64; gs.w_cin = 65;
+    if (!conv2d_ws_geom_ok(gs) || conv2d_ws_tail_geom_ok(gs) || !conv_mfma_supported(gs, precision)) continue;
+    v.cg = gs;
+    v.d.in0 = c.d.in0;
+    v.exo_src = c.d.in1;
+    v.fam = Fam::MFMA;
+    c.fused_away = true;
+  }
+}
+
+// ---- inference plans: a skip add right behind a 2-D 64 -> 64 k conv that
+// already carries a residual (the last block's sum + the big skip of
+// sup3rcc/gen_*_5x_1x_* at hi-res) is absorbed into that conv's store on the
+// weights-stationary kernel (ConvGeom::res2): conv.out := add.out, the add
+// never runs.  Verified with the dtypes below, like the concat split.
+static void plan_ws_res2(s3_plan* pl) {
+  const int precision = pl->precision, training = pl->training, output = pl->output;
+  const int n_ops = (int)pl->ops.size();
+  if (training || precision != S3_PREC_BF16 || s3_opt_has(S3O_NO_WS_RES2) || s3_opt_has(S3O_FP32_ACT) ||
+      s3_opt_has(S3O_NO_ADD16) || tl_no_ws_exo)
+    return;
+  for (int i = 0; i < n_ops; ++i) {
+    OpRec& a = pl->ops[i];
+    if (a.d.kind != S3_OP_ADD || a.d.bcast_c || a.fused_away) continue;
+    for (int side = 0; side < 2; ++side) {
+      const int t_conv = side ? a.d.in1 : a.d.in0, t_other = side ? a.d.in0 : a.d.in1;
+      const int rt = root_of(pl, t_conv);
+      if (rt == root_of(pl, output) || rt == root_of(pl, t_other)) continue;
+      int prod = -1, n_use = 0;
       for (int k = 0; k < n_ops; ++k) {
         const s3_op_desc& u = pl->ops[k].d;
+        if (u.kind != S3_OP_VIEW && root_of(pl, u.out) == rt) prod = k;
         for (int id : {u.in0, u.in1, u.res})
-          if (id >= 0 && root_of(pl, id) == ct_) { ++n_use; user = k; }
+          if (id >= 0 && root_of(pl, id) == rt) ++n_use;
       }
-      if (n_use != 1 || user <= i) continue;
-      OpRec& v = pl->ops[user];
-      if (v.d.kind != S3_OP_CONV || root_of(pl, v.d.in0) != ct_ || v.cg.Cin != 65) continue;
-      ConvGeom gs = v.cg;
-      gs.Cin = 64; gs.w_cin = 65;
-      if (!conv2d_ws_geom_ok(gs) || conv2d_ws_tail_geom_ok(gs) || !conv_mfma_supported(gs, precision)) continue;
-      v.cg = gs;
-      v.d.in0 = c.d.in0;
-      v.exo_src = c.d.in1;
-      v.mfma = true;
-      v.fewpos = v.gconv = v.halo32 = v.halo_s2 = v.tail_x3 = false;
-      c.fused_away = true;
+      if (prod < 0 || prod >= i || n_use != 1) continue;
+      OpRec& c = pl->ops[prod];
+      if (c.d.kind != S3_OP_CONV || c.res2_src >= 0 || c.d.res < 0 || c.cg.act != S3_ACT_NONE || c.cg.d2s != 1 ||
+          c.cg.w_cin || c.fam != Fam::MFMA || !conv2d_ws_geom_ok(c.cg) || conv2d_ws_tail_geom_ok(c.cg))
+        continue;
+      // (the other operand must exist before the conv runs)
+      int prod_other = -1;
+      for (int k = 0; k < n_ops; ++k)
+        if (pl->ops[k].d.kind != S3_OP_VIEW && root_of(pl, pl->ops[k].d.out) == root_of(pl, t_other)) prod_other = k;
+      if (prod_other >= prod) continue;
+      c.res2_src = t_other;
+      c.d.out = a.d.out;
+      a.fused_away = true;
+      break;
     }
   }
+}
 
-  // ---- inference plans: a skip add right behind a 2-D 64 -> 64 k conv that
-  // already carries a residual (the last block's sum + the big skip of
-  // sup3rcc/gen_*_5x_1x_* at hi-res) is absorbed into that conv's store on the
-  // weights-stationary kernel (ConvGeom::res2): conv.out := add.out, the add
-  // never runs.  Verified with the dtypes below, like the concat split.
-  if (!training && precision == S3_PREC_BF16 && !s3_opt_has(S3O_NO_WS_RES2) && !s3_opt_has(S3O_FP32_ACT) &&
-      !s3_opt_has(S3O_NO_ADD16) && !tl_no_ws_exo) {
-    for (int i = 0; i < n_ops; ++i) {
-      OpRec& a = pl->ops[i];
-      if (a.d.kind != S3_OP_ADD || a.d.bcast_c || a.fused_away) continue;
-      for (int side = 0; side < 2; ++side) {
-        const int t_conv = side ? a.d.in1 : a.d.in0, t_other = side ? a.d.in0 : a.d.in1;
-        const int rt = root_of(pl, t_conv);
-        if (rt == root_of(pl, output) || rt == root_of(pl, t_other)) continue;
-        int prod = -1, n_use = 0;
-        for (int k = 0; k < n_ops; ++k) {
-          const s3_op_desc& u = pl->ops[k].d;
-          if (u.kind != S3_OP_VIEW && root_of(pl, u.out) == rt) prod = k;
-          for (int id : {u.in0, u.in1, u.res})
-            if (id >= 0 && root_of(pl, id) == rt) ++n_use;
-        }
-        if (prod < 0 || prod >= i || n_use != 1) continue;
-        OpRec& c = pl->ops[prod];
-        if (c.d.kind != S3_OP_CONV || c.res2_src >= 0 || c.d.res < 0 || c.cg.act != S3_ACT_NONE || c.cg.d2s != 1 ||
-            c.cg.w_cin || !c.mfma || !conv2d_ws_geom_ok(c.cg) || conv2d_ws_tail_geom_ok(c.cg))
-          continue;
-        // (the other operand must exist before the conv runs)
-        int prod_other = -1;
-        for (int k = 0; k < n_ops; ++k)
-          if (pl->ops[k].d.kind != S3_OP_VIEW && root_of(pl, pl->ops[k].d.out) == root_of(pl, t_other)) prod_other = k;
-        if (prod_other >= prod) continue;
-        c.res2_src = t_other;
-        c.d.out = a.d.out;
-        a.fused_away = true;
-        break;
-      }
-    }
-  }
-
-  // ---- activation dtypes.  Inference plans in bf16 mode keep a tensor in
-  // bf16 when its producer can write it (MFMA conv, direct conv, index op) and
-  // EVERY consumer can read it (MFMA conv input / residual, index op);
-  // everything else — plan inputs/outputs, training plans, f32 mode — is fp32.
-  // Training plans (SUP3R_AMD_BF16_TRAIN_ACT=0 opts out): the same, but a saved
-  // activation is also read by the backward pass — a tensor stays bf16 only if
-  // every conv that consumes it takes its weight gradient through the
-  // transpose-read bf16 kernel (which stages bf16 directly); the LeakyReLU
-  // mask pass reads the sign of a bf16 output; gradients stay fp32.  The
-  // forward is then bit-identical to the bf16 inference plan of the trunk.
+// ---- activation dtypes.  Inference plans in bf16 mode keep a tensor in
+// bf16 when its producer can write it (MFMA conv, direct conv, index op) and
+// EVERY consumer can read it (MFMA conv input / residual, index op);
+// everything else — plan inputs/outputs, training plans, f32 mode — is fp32.
+// Training plans (SUP3R_AMD_BF16_TRAIN_ACT=0 opts out): the same, but a saved
+// activation is also read by the backward pass — a tensor stays bf16 only if
+// every conv that consumes it takes its weight gradient through the
+// transpose-read bf16 kernel (which stages bf16 directly); the LeakyReLU
+// mask pass reads the sign of a bf16 output; gradients stay fp32.  The
+// forward is then bit-identical to the bf16 inference plan of the trunk.
+static void plan_dtypes(s3_plan* pl) {
+  const int precision = pl->precision, training = pl->training, output = pl->output;
+  const int n_tensors = (int)pl->t.size();
   const bool train16 = training && precision == S3_PREC_BF16 && !s3_opt_has(S3O_FP32_ACT) &&
                        !(s3_opt_has(S3O_BF16_TRAIN_ACT) && s3_opt_int(S3O_BF16_TRAIN_ACT, 0) == 0);
   if ((!training || train16) && precision == S3_PREC_BF16 && !s3_opt_has(S3O_FP32_ACT)) {
@@ -1041,7 +1103,7 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
     // numerically); as a residual the fp32 value is kept
     std::vector<char> fewch_out(n_tensors, 0);
     for (auto& o : pl->ops)
-      if (o.d.kind == S3_OP_CONV && !o.mfma && o.gconv && o.cg.Cin <= 4) fewch_out[root_of(pl, o.d.out)] = 1;
+      if (o.d.kind == S3_OP_CONV && o.gconv() && o.cg.Cin <= 4) fewch_out[root_of(pl, o.d.out)] = 1;
     while (changed) {
       changed = false;
       for (auto& o : pl->ops) {
@@ -1050,7 +1112,7 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
         switch (d.kind) {
           case S3_OP_CONV:
             if (training && d.res >= 0 && fewch_out[root_of(pl, d.res)]) demote(d.res, changed);
-            if (o.mfma) {
+            if (o.fam == Fam::MFMA) {
               if (!conv_mfma_bf16_out_ok(o.cg)) demote(d.out, changed);
               if (o.cg.Cin % 8 != 0) demote(d.in0, changed);   // (logical-axes kernel: 16-B bf16 chunks)
               // (a saved bf16 input is re-read by the weight gradient: the
@@ -1058,14 +1120,14 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
               // (round 5: ... and so does the 2-D weight gradient, so that the
               // 64 -> 64 layers of a 2-D training plan keep bf16 cells and run
               // forward on the weights-stationary kernel)
-              if (training && !o.wgrad_bf16 && !(o.wgrad_bf16_gen && !s3_opt_has(S3O_NO_DISC_BF16)) &&
-                  !(o.wgrad_bf16_2d && o.cg.Cin % 8 == 0 && !s3_opt_has(S3O_NO_TRAIN2D_BF16)))
+              if (training && o.wgrad != Wgrad::BF16_TRUNK && !(o.wgrad == Wgrad::BF16_GEN && !s3_opt_has(S3O_NO_DISC_BF16)) &&
+                  !(o.wgrad == Wgrad::BF16_2D && o.cg.Cin % 8 == 0 && !s3_opt_has(S3O_NO_TRAIN2D_BF16)))
                 demote(d.in0, changed);
             } else if (training) {
               // every other conv reads / writes fp32 in training plans — except
               // the hi-res tail conv, whose MFMA forward takes bf16 cells and
               // whose weight gradient (conv_wgrad_tail_kernel) stages them as is
-              const bool tail16 = d.res < 0 && !o.fewpos && o.wgrad_tail && conv_tail_mfma_supported(o.cg);
+              const bool tail16 = d.res < 0 && o.wgrad == Wgrad::TAIL && conv_tail_mfma_supported(o.cg);
               // ... and the hi-res discriminator pair: the few-channel conv
               // (C_in <= 4) may write bf16 when its consumer is a gather-MFMA
               // conv (bf16 cells in, C_in % 8 == 0) whose weight gradient is
@@ -1075,9 +1137,9 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
               // keeps it to the first pair, SUP3R_AMD_NO_DISC_BF16 turns it off)
               const bool disc16 = !s3_opt_has(S3O_NO_DISC_BF16);
               const bool deep16 = disc16 && !(s3_opt_has(S3O_DISC_BF16) && s3_opt_int(S3O_DISC_BF16, 0) == 1);
-              const bool gc_in16 = disc16 && o.gconv && (!o.halo32 || deep16) && d.res < 0 && o.wgrad_bf16_gen &&
+              const bool gc_in16 = disc16 && o.gconv() && (o.fam != Fam::HALO32 || deep16) && d.res < 0 && o.wgrad == Wgrad::BF16_GEN &&
                                    o.cg.Cin % 8 == 0;
-              const bool gc_out16 = disc16 && o.gconv && d.res < 0 && o.cg.Cout % 8 == 0 &&
+              const bool gc_out16 = disc16 && o.gconv() && d.res < 0 && o.cg.Cout % 8 == 0 &&
                                     (o.cg.Cin == 2 || o.cg.Cin == 4 || (deep16 && o.cg.Cin % 8 == 0));
               if (!tail16 && !gc_in16) demote(d.in0, changed);
               demote(d.res, changed);
@@ -1085,11 +1147,11 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
             } else {
               // the direct kernels read fp32, except the small-channel tail
               // convs (MFMA C_in = 8 / sliding window) which take bf16 cells
-              const bool small = d.res < 0 && !o.fewpos &&
+              const bool small = d.res < 0 && !o.fewpos() &&
                                  (conv_small_supported(o.cg, 1) || conv_tail_mfma_supported(o.cg));
               if (!small) demote(d.in0, changed);
               demote(d.res, changed);
-              if (small || o.fewpos) demote(d.out, changed);
+              if (small || o.fewpos()) demote(d.out, changed);
             }
             break;
           case S3_OP_REPEAT_T: case S3_OP_D2S: case S3_OP_PAD: case S3_OP_CROP:
@@ -1123,110 +1185,94 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
     o.io.in_bf16 = pl->t[root_of(pl, o.d.in0)].dtype;
     o.io.out_bf16 = pl->t[root_of(pl, o.d.out)].dtype;
     o.io.res_bf16 = o.d.res >= 0 ? pl->t[root_of(pl, o.d.res)].dtype : 0;
-    if (s3_opt_has(S3O_TRACE))
-      fprintf(stderr, "[plan] conv %d->%d %s: mfma %d fewpos %d gconv %d halo32 %d | in16 %d out16 %d res16 %d | "
-              "wgrad bf16 %d gen %d 2d %d c2 %d tail %d mfma %d | dgrad mfma %d c2 %d s2 %d gconv %d\n",
-              o.cg.Cin, o.cg.Cout, training ? "train" : "infer", (int)o.mfma, (int)o.fewpos, (int)o.gconv,
-              (int)o.halo32, o.io.in_bf16, o.io.out_bf16, o.io.res_bf16, (int)o.wgrad_bf16, (int)o.wgrad_bf16_gen,
-              (int)o.wgrad_bf16_2d, (int)o.wgrad_c2, (int)o.wgrad_tail, (int)o.wgrad_mfma, (int)o.dgrad_mfma,
-              (int)o.dgrad_c2, (int)o.dgrad_s2, (int)o.gconv_dgrad);
   }
+}
 
-  for (auto& o : pl->ops)
-    if (o.d.kind == S3_OP_CONV && o.mfma && conv_mfma_is_gen(o.cg, precision) && o.cg.in_rep <= 1 &&
-        conv2d_ws_supported(o.cg, precision, o.io, o.d.res >= 0))
-      o.cg.ws_only = 1;
+// ---- activation-adjoint fusion (training): a conv whose data gradient runs
+// on conv_dgrad_s2_kernel and whose input is the fp32 output of an activated
+// conv with no other consumer applies that conv's mask in its own store
+static void plan_mask_fusion(s3_plan* pl) {
+  const int training = pl->training, output = pl->output;
+  const int n_ops = (int)pl->ops.size(), n_tensors = (int)pl->t.size();
+  if (!training) return;
+  std::vector<int> ncons(n_tensors, 0), prod(n_tensors, -1);
+  for (int i = 0; i < n_ops; ++i) {
+    const s3_op_desc& d = pl->ops[i].d;
+    for (int id : {d.in0, d.in1, d.res})
+      if (id >= 0) ++ncons[root_of(pl, id)];
+    if (d.kind != S3_OP_VIEW) prod[root_of(pl, d.out)] = i;
+  }
   for (auto& o : pl->ops) {
-    if (o.d.kind != S3_OP_CONV || (o.exo_src < 0 && o.res2_src < 0)) continue;
-    if (conv2d_ws_supported(o.cg, precision, o.io, o.d.res >= 0) &&
-        (o.res2_src < 0 || pl->t[root_of(pl, o.res2_src)].dtype == 1))
-      continue;
-    // (a consumer of the 64-channel tensor that needs fp32 cells, ...): build
-    // the plan again with the concat as it is written
-    delete pl;
-    ++tl_no_ws_exo;
-    const int rc = s3_plan_create_opt(ctx, params, tensors, n_tensors, ops, n_ops, inputs, n_inputs, output,
-                                      precision, training, options, out);
-    --tl_no_ws_exo;
-    return rc;
-  }
-
-  // ---- activation-adjoint fusion (training): a conv whose data gradient runs
-  // on conv_dgrad_s2_kernel and whose input is the fp32 output of an activated
-  // conv with no other consumer applies that conv's mask in its own store
-  if (training) {
-    std::vector<int> ncons(n_tensors, 0), prod(n_tensors, -1);
-    for (int i = 0; i < n_ops; ++i) {
-      const s3_op_desc& d = pl->ops[i].d;
-      for (int id : {d.in0, d.in1, d.res})
-        if (id >= 0) ++ncons[root_of(pl, id)];
-      if (d.kind != S3_OP_VIEW) prod[root_of(pl, d.out)] = i;
+    if (o.d.kind == S3_OP_CONV) {
+      const int pr = prod[root_of(pl, o.d.in0)];
+      if (pr >= 0 && pl->ops[pr].d.kind == S3_OP_CONV) o.in_prod = pr;
     }
-    for (auto& o : pl->ops) {
-      if (o.d.kind == S3_OP_CONV) {
-        const int pr = prod[root_of(pl, o.d.in0)];
-        if (pr >= 0 && pl->ops[pr].d.kind == S3_OP_CONV) o.in_prod = pr;
-      }
-      // (the stride-2 dgrad kernel masks from an fp32 y; the frame fold of the
-      // halo-tile dgrad from fp32 or bf16)
-      const bool fold = (o.dgrad_mfma && !o.dgrad_valid) ||
-                        (o.fewpos && o.fp_mfma && o.cg.pad_mode == S3_PAD_REFLECT && !o.dgrad_chunked &&
-                         !o.dgrad_s2 && !o.dgrad_c2 && !o.gconv_dgrad);   // (the one-launch fewpos dgrad folds its frame too)
-      if (o.d.kind != S3_OP_CONV || !(o.dgrad_s2 || fold)) continue;
-      const int r = root_of(pl, o.d.in0);
-      const int pi = prod[r];
-      if (pi < 0 || ncons[r] != 1 || r == root_of(pl, output) || pl->t[r].is_input) continue;
+    // (the stride-2 dgrad kernel masks from an fp32 y; the frame fold of the
+    // halo-tile dgrad from fp32 or bf16)
+    const bool fold = (dgrad_is_mfma(o.dgrad) && !dgrad_is_valid(o.dgrad)) ||
+                      (o.dgrad == Dgrad::FEWPOS_MFMA && o.cg.pad_mode == S3_PAD_REFLECT);   // (the one-launch fewpos dgrad folds its frame too)
+    if (o.d.kind != S3_OP_CONV || !(dgrad_is_s2(o.dgrad) || fold)) continue;
+    const int r = root_of(pl, o.d.in0);
+    const int pi = prod[r];
+    if (pi < 0 || ncons[r] != 1 || r == root_of(pl, output) || pl->t[r].is_input) continue;
 
-      if (fold && (o.cg.Cin & 3)) continue;
-      const OpRec& po = pl->ops[pi];
-      if (po.d.kind == S3_OP_CONV && po.cg.act != S3_ACT_NONE && po.cg.d2s == 1 && po.d.res < 0)
-        o.mask_prod = pi;
-    }
+    if (fold && (o.cg.Cin & 3)) continue;
+    const OpRec& po = pl->ops[pi];
+    if (po.d.kind == S3_OP_CONV && po.cg.act != S3_ACT_NONE && po.cg.d2s == 1 && po.d.res < 0)
+      o.mask_prod = pi;
   }
+}
 
-  // ---- inference plans: a temporal repeat whose only consumer is a conv on
-  // the persistent trunk kernel is read through that kernel's halo index
-  // (cell t of the repeated tensor = cell t / rep of the source) instead of
-  // being written out and read back (at C2 batch 32 the 96 -> 288
-  // repeat alone is a 400 MB store + load per forward)
-  if (!training && precision == S3_PREC_BF16 && !s3_opt_has(S3O_NO_REPEAT_FUSE)) {
-    for (int i = 0; i < n_ops; ++i) {
-      OpRec& r = pl->ops[i];
-      if (r.d.kind != S3_OP_REPEAT_T || !conv_mfma_persist_rep_ok(r.d.rep)) continue;
-      const int rt = root_of(pl, r.d.out);
-      if (rt == root_of(pl, output) || pl->t[root_of(pl, r.d.in0)].dtype != pl->t[rt].dtype) continue;
-      // every consumer is a plain 64 -> 64 trunk conv on the persistent kernel
-      // ('same' extents, one padding for all axes, no depth-to-space store)
-      // taking it as the input or as the residual — SkipConnection sources sit
-      // right behind the last temporal expansion in the reference's generators
-      // — and carries no other repeat factor yet
-      bool ok = true;
-      int n_use = 0;
-      for (int k = 0; k < n_ops && ok; ++k) {
-        const OpRec& c = pl->ops[k];
-        const bool as_in = c.d.in0 >= 0 && root_of(pl, c.d.in0) == rt;
-        const bool as_in1 = c.d.in1 >= 0 && root_of(pl, c.d.in1) == rt;
-        const bool as_res = c.d.res >= 0 && root_of(pl, c.d.res) == rt;
-        if (!as_in && !as_in1 && !as_res) continue;
-        ++n_use;
-        ok = k > i && !as_in1 && c.d.kind == S3_OP_CONV && c.mfma &&
-             conv_mfma_persist_supported(ctx, c.cg, c.io, c.d.res >= 0) && c.cg.d2s == 1 && c.cg.Cout == 64 &&
-             c.cg.O[2] < 32768 && c.cg.O[2] % r.d.rep == 0;
-        for (int q = 0; q < 3; ++q) ok = ok && c.cg.lo[q] == c.cg.lo[0] && c.cg.O[q] == c.cg.D[q];
-        const int have = c.cg.in_rep > 1 ? c.cg.in_rep : c.cg.res_rep;
-        if (have > 1 && have != r.d.rep) ok = false;
-      }
-      if (!ok || !n_use) continue;
-      for (int k = i + 1; k < n_ops; ++k) {
-        OpRec& c = pl->ops[k];
-        if (c.d.kind != S3_OP_CONV) continue;
-        if (root_of(pl, c.d.in0) == rt) { c.cg.in_rep = r.d.rep; c.rep_src = r.d.in0; }
-        if (c.d.res >= 0 && root_of(pl, c.d.res) == rt) { c.cg.res_rep = r.d.rep; c.res_src = r.d.in0; }
-      }
-      r.fused_away = true;
+// ---- inference plans: a temporal repeat whose only consumer is a conv on
+// the persistent trunk kernel is read through that kernel's halo index
+// (cell t of the repeated tensor = cell t / rep of the source) instead of
+// being written out and read back (at C2 batch 32 the 96 -> 288
+// repeat alone is a 400 MB store + load per forward)
+static void plan_repeat_fusion(s3_plan* pl) {
+  s3_ctx* ctx = pl->ctx;
+  const int precision = pl->precision, training = pl->training, output = pl->output;
+  const int n_ops = (int)pl->ops.size();
+  if (training || precision != S3_PREC_BF16 || s3_opt_has(S3O_NO_REPEAT_FUSE)) return;
+  for (int i = 0; i < n_ops; ++i) {
+    OpRec& r = pl->ops[i];
+    if (r.d.kind != S3_OP_REPEAT_T || !conv_mfma_persist_rep_ok(r.d.rep)) continue;
+    const int rt = root_of(pl, r.d.out);
+    if (rt == root_of(pl, output) || pl->t[root_of(pl, r.d.in0)].dtype != pl->t[rt].dtype) continue;
+    // every consumer is a plain 64 -> 64 trunk conv on the persistent kernel
+    // ('same' extents, one padding for all axes, no depth-to-space store)
+    // taking it as the input or as the residual — SkipConnection sources sit
+    // right behind the last temporal expansion in the reference's generators
+    // — and carries no other repeat factor yet
+    bool ok = true;
+    int n_use = 0;
+    for (int k = 0; k < n_ops && ok; ++k) {
+      const OpRec& c = pl->ops[k];
+      const bool as_in = c.d.in0 >= 0 && root_of(pl, c.d.in0) == rt;
+      const bool as_in1 = c.d.in1 >= 0 && root_of(pl, c.d.in1) == rt;
+      const bool as_res = c.d.res >= 0 && root_of(pl, c.d.res) == rt;
+      if (!as_in && !as_in1 && !as_res) continue;
+      ++n_use;
+      ok = k > i && !as_in1 && c.d.kind == S3_OP_CONV && c.fam == Fam::MFMA &&
+           conv_mfma_persist_supported(ctx, c.cg, c.io, c.d.res >= 0) && c.cg.d2s == 1 && c.cg.Cout == 64 &&
+           c.cg.O[2] < 32768 && c.cg.O[2] % r.d.rep == 0;
+      for (int q = 0; q < 3; ++q) ok = ok && c.cg.lo[q] == c.cg.lo[0] && c.cg.O[q] == c.cg.D[q];
+      const int have = c.cg.in_rep > 1 ? c.cg.in_rep : c.cg.res_rep;
+      if (have > 1 && have != r.d.rep) ok = false;
     }
+    if (!ok || !n_use) continue;
+    for (int k = i + 1; k < n_ops; ++k) {
+      OpRec& c = pl->ops[k];
+      if (c.d.kind != S3_OP_CONV) continue;
+      if (root_of(pl, c.d.in0) == rt) { c.cg.in_rep = r.d.rep; c.rep_src = r.d.in0; }
+      if (c.d.res >= 0 && root_of(pl, c.d.res) == rt) { c.cg.res_rep = r.d.rep; c.res_src = r.d.in0; }
+    }
+    r.fused_away = true;
   }
+}
 
+static int plan_arena(s3_plan* pl, size_t& max_t) {
+  const int training = pl->training, output = pl->output;
+  const int n_ops = (int)pl->ops.size(), n_tensors = (int)pl->t.size();
   // ---- static arena planning.  Training keeps every tensor; inference
   // reuses buffers by liveness (greedy best-fit).
   std::vector<int> last_use(n_tensors, -1);
@@ -1266,17 +1312,24 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
   pl->buffer_bytes = bsize;
   for (size_t b = 0; b < bsize.size(); ++b) {
     int rc = plan_alloc(pl, (void**)&pl->buffers[b], bsize[b]);
-    if (rc) { s3_plan_destroy(pl); return rc; }
+    if (rc) return rc;
   }
   for (int i = 0; i < n_tensors; ++i)
     if (pl->t[i].buffer >= 0) pl->t[i].ptr = pl->buffers[pl->t[i].buffer];
+  return S3_OK;
+}
+
+static int plan_workspace(s3_plan* pl, const WorkspaceSizes& ws, size_t max_t) {
+  s3_ctx* ctx = pl->ctx;
+  const int precision = pl->precision, training = pl->training;
+  const int n_tensors = (int)pl->t.size();
   if (training) {
     for (int i = 0; i < n_tensors; ++i) {
       if (pl->t[i].alias_root >= 0) continue;
       int rc = plan_alloc(pl, (void**)&pl->t[i].gptr, (size_t)pl->t[i].numel * sizeof(float));
-      if (rc) { s3_plan_destroy(pl); return rc; }
+      if (rc) return rc;
     }
-    int rc = plan_alloc(pl, (void**)&pl->dpre, max_dpre);
+    int rc = plan_alloc(pl, (void**)&pl->dpre, ws.dpre);
     // bf16 copy of dPre for the MFMA gradient kernels (they round their
     // operand to bf16 anyway; a bf16 source halves the bytes they stage, and
     // the persistent data gradient / the wave-specialised weight gradient take
@@ -1290,28 +1343,28 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
         if (rc || o.d.kind != S3_OP_CONV) continue;
         // (... and the gather-MFMA adjoint of the strided / valid discriminator
         // convs: a lane's 8 channels of a dPre cell are one 16-B load)
-        const bool gadj = o.gconv_dgrad && (o.cg.Cout & 7) == 0 && o.cg.pad_mode != S3_PAD_REFLECT &&
+        const bool gadj = o.dgrad == Dgrad::GCONV && (o.cg.Cout & 7) == 0 && o.cg.pad_mode != S3_PAD_REFLECT &&
                           !s3_opt_has(S3O_NO_GCONV_DY16);
-        if (!gadj && (!o.dgrad_mfma || o.dgrad_fewch || (o.cg.Cout & 3))) continue;
-        if (o.dgrad_gen && (o.cg.Cout & 7)) continue;   // (16-B bf16 chunks of a dPre cell)
-        if (o.dgrad_chunked && ((o.cg.Cout & 7) || s3_opt_has(S3O_NO_CHUNKED_DY16))) continue;
+        if (!gadj && (!dgrad_is_mfma(o.dgrad) || o.dgrad == Dgrad::FEWCH || (o.cg.Cout & 3))) continue;
+        if (o.dgrad == Dgrad::GEN && (o.cg.Cout & 7)) continue;   // (16-B bf16 chunks of a dPre cell)
+        if (dgrad_is_chunked(o.dgrad) && ((o.cg.Cout & 7) || s3_opt_has(S3O_NO_CHUNKED_DY16))) continue;
         o.use16 = true;
         max16 = std::max(max16, (size_t)pl->t[root_of(pl, o.d.out)].numel * 2);
         // the reflect-padded 64 -> 64 trunk conv on the persistent kernel:
         // its padded frame is written — and folded from — as bf16 (round 4)
-        o.dgrad_frame16 = training && o.dgrad_mfma && !o.dgrad_valid && !o.dgrad_chunked && !o.dgrad_fewch &&
+        o.dgrad_frame16 = training && (o.dgrad == Dgrad::MFMA_FRAME || o.dgrad == Dgrad::GEN) &&
                           o.dg.Cout == 64 && (o.cg.Cin & 3) == 0 && o.cg.pad_mode == S3_PAD_REFLECT &&
                           conv_mfma_persist_dgrad_supported(ctx, o.dg) && !s3_opt_has(S3O_NO_FRAME16);
         // ... and so is the frame of a 2-D 64 -> 64 k conv's data gradient on the
         // weights-stationary kernel (round 5)
-        if (training && o.dgrad_gen && !o.dgrad_valid && conv2d_ws_frame_geom_ok(o.dg) &&
+        if (training && o.dgrad == Dgrad::GEN && conv2d_ws_frame_geom_ok(o.dg) &&
             !s3_opt_has(S3O_NO_FRAME16) && !s3_opt_on(S3O_NO_CONV2D_WS))
           o.dgrad_frame16 = true;
       }
       // ... and for the stride-2 data gradient that stores dPre of the
       // few-channel conv below it as bf16 only (see the dgrad_s2 branch)
       for (auto& o : pl->ops)
-        if (o.d.kind == S3_OP_CONV && o.dgrad_s2 && o.mask_prod >= 0 && pl->ops[o.mask_prod].wgrad_c2 &&
+        if (o.d.kind == S3_OP_CONV && dgrad_is_s2(o.dgrad) && o.mask_prod >= 0 && pl->ops[o.mask_prod].wgrad == Wgrad::C2 &&
             conv_dgrad_s2_out16_ok(o.cg))
           max16 = std::max(max16, (size_t)pl->t[root_of(pl, o.d.in0)].numel * 2);
       if (!rc && max16) rc = plan_alloc(pl, &pl->dpre16, max16);
@@ -1320,77 +1373,77 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
     if (!rc) rc = plan_alloc(pl, (void**)&pl->gtmp, max_t);
     if (!rc) rc = plan_alloc(pl, (void**)&pl->bsum, (size_t)4096 * 256 * sizeof(float));
     if (!rc) rc = plan_alloc(pl, (void**)&pl->bsum2, (size_t)4096 * 256 * sizeof(float));
-    if (!rc && max_partial) {
-      rc = plan_alloc(pl, (void**)&pl->wg_partial, max_partial);
-      pl->wg_partial_bytes = max_partial;
+    if (!rc && ws.partial) {
+      rc = plan_alloc(pl, (void**)&pl->wg_partial, ws.partial);
+      pl->wg_partial_bytes = ws.partial;
     }
-    if (!rc && max_dxp) rc = plan_alloc(pl, (void**)&pl->dxp, max_dxp);
+    if (!rc && ws.dxp) rc = plan_alloc(pl, (void**)&pl->dxp, ws.dxp);
     for (auto& o : pl->ops) {
-      if (rc || o.d.kind != S3_OP_CONV || !o.dgrad_mfma) continue;
+      if (rc || o.d.kind != S3_OP_CONV || !dgrad_is_mfma(o.dgrad)) continue;
       rc = plan_alloc(pl, (void**)&o.dg_w32, (size_t)27 * o.cg.Cin * o.cg.Cout * sizeof(float));
-      if (!rc && o.dgrad_chunked) {
+      if (!rc && dgrad_is_chunked(o.dgrad)) {
         for (int k = 0; !rc && k < (o.cg.Cout + 63) / 64; ++k)
           rc = plan_alloc(pl, &o.dgc_wbf[k], conv_mfma_packed_bytes(o.dg, precision));
         continue;
       }
       if (!rc && precision != S3_PREC_F32)
-        rc = plan_alloc(pl, &o.dg_wbf, o.dgrad_fewch ? conv_gconv_packed_bytes(o.dg, 0, precision == S3_PREC_BF16X3)
+        rc = plan_alloc(pl, &o.dg_wbf, o.dgrad == Dgrad::FEWCH ? conv_gconv_packed_bytes(o.dg, 0, precision == S3_PREC_BF16X3)
                                                      : conv_mfma_packed_bytes(o.dg, precision));
     }
-    if (rc) { s3_plan_destroy(pl); return rc; }
+    if (rc) return rc;
   }
-  if (max_fp) {
-    int rc = plan_alloc(pl, (void**)&pl->fp_partial, max_fp);
-    if (rc) { s3_plan_destroy(pl); return rc; }
-    pl->fp_partial_bytes = max_fp;
+  if (ws.fp) {
+    int rc = plan_alloc(pl, (void**)&pl->fp_partial, ws.fp);
+    if (rc) return rc;
+    pl->fp_partial_bytes = ws.fp;
   }
   if (training) {
     for (auto& o : pl->ops) {
-      if (o.d.kind != S3_OP_CONV || !o.fewpos) continue;
+      if (o.d.kind != S3_OP_CONV || !o.fewpos()) continue;
       int rc = plan_alloc(pl, (void**)&o.fp_wt, (size_t)o.cg.k[0] * o.cg.k[1] * o.cg.k[2] * o.cg.Cin * o.cg.Cout * sizeof(float));
-      if (rc) { s3_plan_destroy(pl); return rc; }
+      if (rc) return rc;
     }
   }
   // packed weights of the MFMA convs
   for (auto& o : pl->ops) {
-    if (o.d.kind == S3_OP_CONV && o.mfma) {
+    if (o.d.kind == S3_OP_CONV && o.fam == Fam::MFMA) {
       int rc = plan_alloc(pl, &o.packed, conv_mfma_packed_bytes(o.cg, precision));
-      if (rc) { s3_plan_destroy(pl); return rc; }
+      if (rc) return rc;
     }
   }
   for (auto& o : pl->ops) {
     if (o.d.kind != S3_OP_CONV) continue;
-    if (o.gconv) {
+    if (o.gconv()) {
       int rc = plan_alloc(pl, &o.gc_w, conv_gconv_packed_bytes(o.cg, 0, precision == S3_PREC_BF16X3));
-      if (rc) { s3_plan_destroy(pl); return rc; }
+      if (rc) return rc;
     }
-    if (o.halo32 || o.halo_s2) {
-      int rc = plan_alloc(pl, &o.h32_w, o.halo32 ? conv_halo32_packed_bytes(o.cg) : conv_halo_s2_packed_bytes(o.cg));
-      if (rc) { s3_plan_destroy(pl); return rc; }
+    if (o.fam == Fam::HALO32 || o.fam == Fam::HALO_S2) {
+      int rc = plan_alloc(pl, &o.h32_w, o.fam == Fam::HALO32 ? conv_halo32_packed_bytes(o.cg) : conv_halo_s2_packed_bytes(o.cg));
+      if (rc) return rc;
     }
-    if (o.dgrad_s2) {
+    if (dgrad_is_s2(o.dgrad)) {
       int rc = plan_alloc(pl, &o.dc2_w, precision == S3_PREC_BF16X3 ? conv_dgrad_s2_x3_packed_bytes(o.cg)
                                                                     : conv_dgrad_s2_packed_bytes(o.cg));
-      if (rc) { s3_plan_destroy(pl); return rc; }
+      if (rc) return rc;
       // its fused activation mask as sign bytes written by the producer's
       // forward kernel (4 B instead of 64 B per position read back)
       if (o.mask_prod >= 0 && precision == S3_PREC_BF16 && !s3_opt_has(S3O_NO_SIGN_BYTES)) {
         OpRec& po = pl->ops[o.mask_prod];
-        if (po.gconv && !po.sign_bytes && conv_gconv_writes_sign_bytes(ctx, po.cg, po.io.out_bf16)) {
+        if (po.gconv() && !po.sign_bytes && conv_gconv_writes_sign_bytes(ctx, po.cg, po.io.out_bf16)) {
           const size_t npos = (size_t)po.cg.N * po.cg.O[0] * po.cg.O[1] * po.cg.O[2];
           rc = plan_alloc(pl, &po.sign_bytes, npos * 4);
-          if (rc) { s3_plan_destroy(pl); return rc; }
+          if (rc) return rc;
         }
       }
     }
-    if (o.dgrad_c2) {
+    if (dgrad_is_c2(o.dgrad)) {
       int rc = plan_alloc(pl, &o.dc2_w, precision == S3_PREC_BF16X3 ? conv_dgrad_c2_x3_packed_bytes()
                                                                     : conv_dgrad_c2_packed_bytes());
-      if (rc) { s3_plan_destroy(pl); return rc; }
+      if (rc) return rc;
     }
-    if (o.gconv_dgrad) {
+    if (o.dgrad == Dgrad::GCONV) {
       int rc = plan_alloc(pl, &o.gc_wt, conv_gconv_packed_bytes(o.cg, 1, precision == S3_PREC_BF16X3));
-      if (rc) { s3_plan_destroy(pl); return rc; }
+      if (rc) return rc;
     }
   }
   // staging copies of the graph inputs: fixed pointers for the hipGraph replay
@@ -1398,14 +1451,22 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
     for (size_t i = 0; i < pl->inputs.size(); ++i) {
       void* st = nullptr;
       int rc = plan_alloc(pl, &st, (size_t)pl->t[pl->inputs[i]].numel * sizeof(float));
-      if (rc) { s3_plan_destroy(pl); return rc; }
+      if (rc) return rc;
       pl->in_stage.push_back((float*)st);
     }
   }
   pl->gwritten.assign(n_tensors, 0);
+  return S3_OK;
+}
+
+static void plan_fused2d(s3_plan* pl) {
+  s3_ctx* ctx = pl->ctx;
+  const int precision = pl->precision, training = pl->training, output = pl->output;
+  const int n_tensors = (int)pl->t.size();
+  const s3_params* params = pl->params;
   // small 2-D conv stacks (the spatial generators at test / C1 sizes): one launch
   // for the whole op list, activations in LDS
-  if (!training && precision == S3_PREC_BF16 && n_inputs == 1) {
+  if (!training && precision == S3_PREC_BF16 && pl->inputs.size() == 1) {
     std::vector<Fused2dLayer> fl;
     bool ok = true;
     for (auto& o : pl->ops) {
@@ -1423,6 +1484,89 @@ extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
     if (s3_opt_has(S3O_TRACE))
       fprintf(stderr, "[plan] fused 2-D whole-network kernel: %s\n", pl->fused2d ? "yes" : "no");
   }
+}
+
+
+// one line per conv under the TRACE option, once the dtypes are known (the
+// tests read the family / gradient kernels from it)
+static void plan_trace(const s3_plan* pl) {
+  if (!s3_opt_has(S3O_TRACE)) return;
+  for (const OpRec& o : pl->ops) {
+    if (o.d.kind != S3_OP_CONV) continue;
+    const Wgrad w = o.wgrad;
+    const Dgrad d = o.dgrad;
+    fprintf(stderr, "[plan] conv %d->%d %s: mfma %d fewpos %d gconv %d halo32 %d | in16 %d out16 %d res16 %d | "
+            "wgrad bf16 %d gen %d 2d %d c2 %d tail %d mfma %d | dgrad mfma %d c2 %d s2 %d gconv %d\n",
+            o.cg.Cin, o.cg.Cout, pl->training ? "train" : "infer", o.fam == Fam::MFMA, o.fewpos(), o.gconv(),
+            o.fam == Fam::HALO32, o.io.in_bf16, o.io.out_bf16, o.io.res_bf16, w == Wgrad::BF16_TRUNK,
+            w == Wgrad::BF16_GEN, w == Wgrad::BF16_2D, w == Wgrad::C2, w == Wgrad::TAIL,
+            w == Wgrad::BF16_TRUNK || w == Wgrad::F32_TRUNK, dgrad_is_mfma(d), dgrad_is_c2(d), dgrad_is_s2(d),
+            d == Dgrad::GCONV);
+  }
+}
+
+extern "C" int s3_plan_create_opt(s3_ctx* ctx, s3_params* params,
+                                  const s3_tensor_desc* tensors, int n_tensors,
+                                  const s3_op_desc* ops, int n_ops,
+                                  const int32_t* inputs, int n_inputs,
+                                  int32_t output, int precision, int training,
+                                  const s3_plan_options* options, s3_plan** out) {
+  if (!ctx || !params || !tensors || !ops || !out) return S3_EINVAL;
+  if (output < 0 || output >= n_tensors) S3_FAIL(ctx, S3_EINVAL, "plan: bad output id");
+  S3Options plan_opt = ctx->opt;
+  if (int orc = apply_options(ctx, plan_opt, options)) return orc;
+  s3_plan* pl = new s3_plan();
+  pl->opt = plan_opt;
+  S3OptScope opt_scope(&pl->opt);
+  pl->ctx = ctx; pl->params = params; pl->precision = precision;
+  pl->training = training; pl->output = output;
+  pl->t.resize(n_tensors);
+  for (int i = 0; i < n_tensors; ++i) {
+    memcpy(pl->t[i].dims, tensors[i].dims, sizeof(int64_t) * 5);
+    pl->t[i].numel = numel5(tensors[i].dims);
+    if (pl->t[i].numel <= 0) { delete pl; S3_FAIL(ctx, S3_EINVAL, "plan: empty tensor"); }
+  }
+  for (int i = 0; i < n_inputs; ++i) {
+    if (inputs[i] < 0 || inputs[i] >= n_tensors) { delete pl; S3_FAIL(ctx, S3_EINVAL, "plan: bad input id"); }
+    pl->inputs.push_back(inputs[i]);
+    pl->t[inputs[i]].is_input = true;
+  }
+  pl->ops.resize(n_ops);
+  WorkspaceSizes ws;
+  if (int rc = plan_select(pl, ops, ws)) { delete pl; return rc; }
+  plan_ws_exo(pl);
+  plan_ws_res2(pl);
+  plan_dtypes(pl);
+  plan_trace(pl);
+  // (2-D convs on the weights-stationary kernel: never launched off it)
+  for (auto& o : pl->ops)
+    if (o.d.kind == S3_OP_CONV && o.fam == Fam::MFMA && conv_mfma_is_gen(o.cg, precision) && o.cg.in_rep <= 1 &&
+        conv2d_ws_supported(o.cg, precision, o.io, o.d.res >= 0))
+      o.cg.ws_only = 1;
+  for (auto& o : pl->ops) {
+    if (o.d.kind != S3_OP_CONV || (o.exo_src < 0 && o.res2_src < 0)) continue;
+    if (conv2d_ws_supported(o.cg, precision, o.io, o.d.res >= 0) &&
+        (o.res2_src < 0 || pl->t[root_of(pl, o.res2_src)].dtype == 1))
+      continue;
+    // (a consumer of the 64-channel tensor that needs fp32 cells, ...): build
+    // the plan again with the concat as it is written
+    delete pl;
+    ++tl_no_ws_exo;
+    const int rc = s3_plan_create_opt(ctx, params, tensors, n_tensors, ops, n_ops, inputs, n_inputs, output,
+                                      precision, training, options, out);
+    --tl_no_ws_exo;
+    return rc;
+  }
+
+  plan_mask_fusion(pl);
+  plan_repeat_fusion(pl);
+  for (auto& o : pl->ops)
+    if (o.d.kind == S3_OP_CONV) o.fwd = resolve_fwd(ctx, o, precision);
+  size_t max_t = 0;
+  int rc = plan_arena(pl, max_t);
+  if (!rc) rc = plan_workspace(pl, ws, max_t);
+  if (rc) { s3_plan_destroy(pl); return rc; }
+  plan_fused2d(pl);
   *out = pl;
   return S3_OK;
 }
@@ -1475,7 +1619,7 @@ static int pack_tables_build(s3_plan* pl) {
     if (o.d.kind != S3_OP_CONV) continue;
     const ConvGeom& g = o.cg;
     const bool k3 = g.k[0] == 3 && g.k[1] == 3 && g.k[2] == 3;
-    if (o.mfma && o.packed && g.Cin == 64 && k3 && !conv_mfma_is_gen(g, pl->precision)) {
+    if (o.fam == Fam::MFMA && o.packed && g.Cin == 64 && k3 && !conv_mfma_is_gen(g, pl->precision)) {
       S3PackJob j;
       j.w = W + P->p[o.d.w].offset;
       j.cout = g.Cout; j.n_ct = (g.Cout + 63) / 64; j.dgrad = 0;
@@ -1484,7 +1628,7 @@ static int pack_tables_build(s3_plan* pl) {
       fwd.push_back(j); pl->pack_fwd_ops.push_back(i);
       pl->pack_fwd_ct = std::max(pl->pack_fwd_ct, j.n_ct);
     }
-    if (pl->training && o.dgrad_mfma && !o.dgrad_gen && !o.dgrad_fewch && !o.dgrad_chunked && o.dg_wbf && g.Cout == 64 && k3 &&
+    if (pl->training && (o.dgrad == Dgrad::MFMA_FRAME || o.dgrad == Dgrad::MFMA_VALID) && o.dg_wbf && g.Cout == 64 && k3 &&
         o.dg.Cin == 64) {
       S3PackJob j;
       j.w = W + P->p[o.d.w].offset;
@@ -1545,7 +1689,39 @@ static int run_op_forward(s3_plan* pl, OpRec& o) {
       const float* w = W + P->p[d.w].offset;
       const float* b = d.b >= 0 ? W + P->p[d.b].offset : nullptr;
       const float* res = d.res >= 0 ? tptr(pl, o.res_src >= 0 ? o.res_src : d.res) : nullptr;
-      if (o.mfma) {
+      switch (o.fwd) {
+        case Fwd::HALO32:
+          if (o.h32_version != P->version) {
+            int rc = launch_conv_halo32_pack(ctx, o.cg, w, o.h32_w);
+            if (rc) return rc;
+            o.h32_version = P->version;
+          }
+          return launch_conv_halo32_fwd(ctx, o.cg, tptr(pl, d.in0), o.h32_w, b, tptr(pl, d.out), o.io.in_bf16,
+                                        o.io.out_bf16);
+        case Fwd::HALO_S2:
+          if (o.h32_version != P->version) {
+            int rc = launch_conv_halo_s2_pack(ctx, o.cg, w, o.h32_w);
+            if (rc) return rc;
+            o.h32_version = P->version;
+          }
+          return launch_conv_halo_s2_fwd(ctx, o.cg, tptr(pl, d.in0), o.h32_w, b, tptr(pl, d.out), o.io.out_bf16);
+        case Fwd::TAIL_X3:
+          return launch_conv_tail_x3(ctx, o.cg, (const float*)tptr(pl, d.in0), w, b, (float*)tptr(pl, d.out));
+        case Fwd::GCONV:
+          if (o.gc_version != P->version) {
+            int rc = launch_gconv_pack(ctx, o.cg, w, o.gc_w, 0, pl->precision == S3_PREC_BF16X3);
+            if (rc) return rc;
+            o.gc_version = P->version;
+          }
+          return launch_gconv_fwd(ctx, o.cg, (const float*)tptr(pl, d.in0), o.gc_w, b, res, tptr(pl, d.out), o.io.out_bf16, o.io.in_bf16,
+                                  pl->precision == S3_PREC_BF16X3, o.sign_bytes);
+        case Fwd::FEWPOS_MFMA:
+          return launch_conv_fewpos_mfma(ctx, o.cg, 0, tptr(pl, d.in0), w, b, res, tptr(pl, d.out));
+        case Fwd::FEWPOS:
+          return launch_conv_fewpos_fwd(ctx, o.cg, tptr(pl, d.in0), w, b, res, tptr(pl, d.out), pl->fp_partial, pl->fp_partial_bytes);
+        default: break;
+      }
+      if (fwd_is_mfma(o.fwd)) {
         if (o.packed_version != P->version) {
           int rc = launch_conv_mfma_pack(ctx, o.cg, pl->precision, w, o.packed);
           if (rc) return rc;
@@ -1556,47 +1732,16 @@ static int run_op_forward(s3_plan* pl, OpRec& o) {
           ConvGeom ge = o.cg;
           if (o.exo_src >= 0) ge.exo = (const float*)tptr(pl, o.exo_src);
           if (o.res2_src >= 0) ge.res2 = tptr(pl, o.res2_src);
-          return launch_conv_mfma_fwd(ctx, ge, pl->precision, tptr(pl, d.in0), wp, b, res, tptr(pl, d.out), o.io);
+          return launch_conv_mfma_fwd_as(ctx, mfma_of(o.fwd), ge, pl->precision, tptr(pl, d.in0), wp, b, res,
+                                         tptr(pl, d.out), o.io);
         }
-        return launch_conv_mfma_fwd(ctx, o.cg, pl->precision, tptr(pl, o.rep_src >= 0 ? o.rep_src : d.in0), wp, b,
-                                    res, tptr(pl, d.out), o.io);
-      }
-      if (o.halo32 && !res) {
-        if (o.h32_version != P->version) {
-          int rc = launch_conv_halo32_pack(ctx, o.cg, w, o.h32_w);
-          if (rc) return rc;
-          o.h32_version = P->version;
-        }
-        return launch_conv_halo32_fwd(ctx, o.cg, tptr(pl, d.in0), o.h32_w, b, tptr(pl, d.out), o.io.in_bf16,
-                                      o.io.out_bf16);
-      }
-      if (o.halo_s2 && !res && o.io.in_bf16) {
-        if (o.h32_version != P->version) {
-          int rc = launch_conv_halo_s2_pack(ctx, o.cg, w, o.h32_w);
-          if (rc) return rc;
-          o.h32_version = P->version;
-        }
-        return launch_conv_halo_s2_fwd(ctx, o.cg, tptr(pl, d.in0), o.h32_w, b, tptr(pl, d.out), o.io.out_bf16);
+        return launch_conv_mfma_fwd_as(ctx, mfma_of(o.fwd), o.cg, pl->precision,
+                                       tptr(pl, o.rep_src >= 0 ? o.rep_src : d.in0), wp, b, res, tptr(pl, d.out), o.io);
       }
       if (pl->win_op >= 0 && &o == &pl->ops[pl->win_op])   // s3_plan_forward_window: checked there
         return launch_conv_tail_mfma(ctx, pl->win_geom, tptr(pl, d.in0), w, b, (float*)tptr(pl, d.out), pl->win_aff);
-      if (o.tail_x3 && !res && !o.io.in_bf16 && !o.io.out_bf16)
-        return launch_conv_tail_x3(ctx, o.cg, (const float*)tptr(pl, d.in0), w, b, (float*)tptr(pl, d.out));
-      if (o.gconv && (!o.io.in_bf16 || o.cg.Cin % 8 == 0) && !o.io.res_bf16 &&
-          (!o.io.out_bf16 || o.cg.Cout % 4 == 0)) {
-        if (o.gc_version != P->version) {
-          int rc = launch_gconv_pack(ctx, o.cg, w, o.gc_w, 0, pl->precision == S3_PREC_BF16X3);
-          if (rc) return rc;
-          o.gc_version = P->version;
-        }
-        return launch_gconv_fwd(ctx, o.cg, (const float*)tptr(pl, d.in0), o.gc_w, b, res, tptr(pl, d.out), o.io.out_bf16, o.io.in_bf16,
-                                pl->precision == S3_PREC_BF16X3, o.sign_bytes);
-      }
-      if (o.fewpos && o.fp_mfma && !o.io.in_bf16 && !o.io.out_bf16)
-        return launch_conv_fewpos_mfma(ctx, o.cg, 0, tptr(pl, d.in0), w, b, res, tptr(pl, d.out));
-      if (o.fewpos && !o.io.in_bf16 && !o.io.out_bf16)
-        return launch_conv_fewpos_fwd(ctx, o.cg, tptr(pl, d.in0), w, b, res, tptr(pl, d.out), pl->fp_partial, pl->fp_partial_bytes);
-      return launch_conv_generic_fwd(ctx, o.cg, tptr(pl, d.in0), w, b, res, tptr(pl, d.out), o.io.out_bf16, o.io.in_bf16);
+      return launch_conv_generic_fwd(ctx, generic_of(o.fwd), o.cg, tptr(pl, d.in0), w, b, res, tptr(pl, d.out),
+                                     o.io.out_bf16, o.io.in_bf16);
     }
     case S3_OP_DENSE: {
       const TensorRec& it = pl->t[d.in0];
@@ -1827,11 +1972,8 @@ extern "C" int s3_plan_op_is_mfma(const s3_plan* pl, int i) {
   if (!pl || i < 0 || i >= (int)pl->ops.size()) return 0;
   S3OptScope opt_scope(&pl->opt);
   const auto& o = pl->ops[i];
-  if (o.d.kind != S3_OP_CONV || !o.mfma) return 0;
-  if (pl->precision == S3_PREC_BF16 &&
-      conv_mfma_persist_supported(pl->ctx, o.cg, o.io, o.d.res >= 0))
-    return 2;
-  return 1;
+  if (o.d.kind != S3_OP_CONV || !fwd_is_mfma(o.fwd)) return 0;
+  return o.fwd == Fwd::MFMA_PERSIST || o.fwd == Fwd::MFMA_PERSIST2 ? 2 : 1;
 }
 
 extern "C" int s3_plan_tensor_dtype(const s3_plan* pl, int32_t id) {
@@ -1859,38 +2001,53 @@ extern "C" int64_t s3_plan_tensor_read(s3_plan* pl, int32_t id, void* host, size
   return (int64_t)bytes;
 }
 
-// which forward kernel run_op_forward / launch_conv_generic_fwd picks for a conv
-static int conv_fwd_kind(const s3_plan* pl, const OpRec& o) {
-  const bool res = o.d.res >= 0;
-  const bool bfp = pl->precision == S3_PREC_BF16;
-  int fwd = S3_FWD_DIRECT;
-  // mirrors run_op_forward / launch_conv_generic_fwd
-  if (o.mfma) {
-    fwd = conv_mfma_is_gen(o.cg, pl->precision)
-              ? (conv2d_ws_supported(o.cg, pl->precision, o.io, res) ||
-                 conv2d_ws_x3_supported(o.cg, pl->precision, o.io, res) ||
-                 conv2d_out_supported(o.cg, pl->precision, o.io, res)    ? S3_FWD_CONV2D_WS
-                 : conv2d_head_supported(o.cg, pl->precision, o.io, res) ? S3_FWD_CONV2D_HEAD
-                                                                         : S3_FWD_MFMA_GEN)
-          : bfp && conv_mfma_persist_supported(pl->ctx, o.cg, o.io, res) ? S3_FWD_MFMA_PERSIST : S3_FWD_MFMA_TILE;
-  } else if (o.halo32 && !res) {
-    fwd = S3_FWD_HALO32;
-  } else if (o.halo_s2 && !res && o.io.in_bf16) {
-    fwd = S3_FWD_HALO_S2;
-  } else if (o.tail_x3 && !res && !o.io.in_bf16 && !o.io.out_bf16) {
-    fwd = S3_FWD_TAIL_MFMA;
-  } else if (o.gconv && (!o.io.in_bf16 || o.cg.Cin % 8 == 0) && !o.io.res_bf16 &&
-             (!o.io.out_bf16 || o.cg.Cout % 4 == 0)) {
-    fwd = o.cg.Cin <= 4 ? S3_FWD_GCONV_FEWCH : S3_FWD_GCONV;
-  } else if (o.fewpos && !o.io.in_bf16 && !o.io.out_bf16) {
-    fwd = S3_FWD_FEWPOS;
-  } else if (o.io.in_bf16 && !o.io.out_bf16 && !res && conv_tail_mfma_supported(o.cg) &&
-             !s3_opt_has(S3O_NO_TAIL_MFMA)) {
-    fwd = S3_FWD_TAIL_MFMA;
-  } else if (!o.io.out_bf16 && !res && conv_small_supported(o.cg, o.io.in_bf16)) {
-    fwd = S3_FWD_SMALL;
+// the public S3_FWD_* / S3_WGRAD_* / S3_DGRAD_* value of a stored choice
+static int fwd_public(const OpRec& o) {
+  switch (o.fwd) {
+    case Fwd::MFMA_TILE: return S3_FWD_MFMA_TILE;
+    case Fwd::MFMA_PERSIST: case Fwd::MFMA_PERSIST2: return S3_FWD_MFMA_PERSIST;
+    case Fwd::MFMA_GEN: return S3_FWD_MFMA_GEN;
+    case Fwd::CONV2D_WS: case Fwd::CONV2D_WS_X3: case Fwd::CONV2D_OUT: return S3_FWD_CONV2D_WS;
+    case Fwd::CONV2D_HEAD: return S3_FWD_CONV2D_HEAD;
+    case Fwd::FEWPOS_MFMA: case Fwd::FEWPOS: return S3_FWD_FEWPOS;
+    case Fwd::GCONV: return o.cg.Cin <= 4 ? S3_FWD_GCONV_FEWCH : S3_FWD_GCONV;
+    case Fwd::HALO32: return S3_FWD_HALO32;
+    case Fwd::HALO_S2: return S3_FWD_HALO_S2;
+    case Fwd::TAIL_X3: case Fwd::TAIL_MFMA: return S3_FWD_TAIL_MFMA;
+    case Fwd::SMALL: return S3_FWD_SMALL;
+    case Fwd::DIRECT: case Fwd::NONE: break;
   }
-  return fwd;
+  return S3_FWD_DIRECT;
+}
+
+static int wgrad_public(Wgrad w) {
+  switch (w) {
+    case Wgrad::FEWPOS_MFMA: case Wgrad::FEWPOS: return S3_WGRAD_FEWPOS;
+    case Wgrad::TAIL: return S3_WGRAD_TAIL;
+    case Wgrad::C2: return S3_WGRAD_C2;
+    case Wgrad::BF16_TRUNK: return S3_WGRAD_BF16_TRUNK;
+    case Wgrad::F32_TRUNK: return S3_WGRAD_F32_TRUNK;
+    case Wgrad::BF16_GEN: return S3_WGRAD_BF16_GEN;
+    case Wgrad::BF16_2D: return S3_WGRAD_BF16_2D;
+    case Wgrad::F32_GEN: return S3_WGRAD_F32_GEN;
+    case Wgrad::DIRECT: break;
+  }
+  return S3_WGRAD_DIRECT;
+}
+
+static int dgrad_public(Dgrad d) {
+  switch (d) {
+    case Dgrad::MFMA_FRAME: case Dgrad::GEN: return S3_DGRAD_MFMA_FRAME;
+    case Dgrad::MFMA_VALID: return S3_DGRAD_MFMA_VALID;
+    case Dgrad::FEWCH: return S3_DGRAD_FEWCH_FRAME;
+    case Dgrad::CHUNKED_FRAME: case Dgrad::CHUNKED_VALID: return S3_DGRAD_MFMA_CHUNKED;
+    case Dgrad::C2: case Dgrad::C2_X3: return S3_DGRAD_C2;
+    case Dgrad::S2: case Dgrad::S2_X3: return S3_DGRAD_S2;
+    case Dgrad::GCONV: return S3_DGRAD_GCONV;
+    case Dgrad::FEWPOS_MFMA: case Dgrad::FEWPOS: return S3_DGRAD_FEWPOS;
+    case Dgrad::DIRECT: break;
+  }
+  return S3_DGRAD_DIRECT;
 }
 
 extern "C" int s3_plan_op_info(const s3_plan* pl, int i, int32_t* out, int cap) {
@@ -1900,7 +2057,7 @@ extern "C" int s3_plan_op_info(const s3_plan* pl, int i, int32_t* out, int cap) 
   int32_t v[S3_OPINFO_COUNT] = {0};
   v[S3_OPINFO_KIND] = o.d.kind;
   if (o.d.kind == S3_OP_CONV) {
-    int fwd = conv_fwd_kind(pl, o);
+    int fwd = fwd_public(o);
     const bool fused = pl->fused2d && !pl->training && !s3_opt_has(S3O_NO_FUSED2D);
     if (fused) fwd = S3_FWD_FUSED2D;
     v[S3_OPINFO_FWD] = fwd;
@@ -1911,28 +2068,10 @@ extern "C" int s3_plan_op_info(const s3_plan* pl, int i, int32_t* out, int cap) 
     v[S3_OPINFO_FWD_BF16_OPS] = (pl->precision == S3_PREC_BF16 &&
                                  (fwd == S3_FWD_FUSED2D || fwd == S3_FWD_MFMA_TILE || fwd == S3_FWD_MFMA_GEN || fwd == S3_FWD_CONV2D_WS || fwd == S3_FWD_CONV2D_HEAD || fwd == S3_FWD_MFMA_PERSIST || fwd == S3_FWD_HALO32 || fwd == S3_FWD_HALO_S2 ||
                                   fwd == S3_FWD_GCONV || fwd == S3_FWD_GCONV_FEWCH || fwd == S3_FWD_TAIL_MFMA)) ? 1 : 0;
-    v[S3_OPINFO_FEWPOS_MFMA] = (o.fp_mfma || o.fp_wg_mfma) ? 1 : 0;
+    v[S3_OPINFO_FEWPOS_MFMA] = (o.fam == Fam::FEWPOS_MFMA || o.wgrad == Wgrad::FEWPOS_MFMA) ? 1 : 0;
     if (pl->training) {
-      int wg = S3_WGRAD_DIRECT;
-      if (o.fewpos || (o.fewpos_wgrad && !o.io.in_bf16)) wg = S3_WGRAD_FEWPOS;
-      else if (o.wgrad_tail) wg = S3_WGRAD_TAIL;
-      else if (o.wgrad_c2) wg = S3_WGRAD_C2;
-      else if (o.wgrad_bf16_2d) wg = S3_WGRAD_BF16_2D;
-      else if (o.wgrad_bf16_gen) wg = S3_WGRAD_BF16_GEN;
-      else if (o.wgrad_gen) wg = S3_WGRAD_F32_GEN;
-      else if (o.wgrad_bf16) wg = S3_WGRAD_BF16_TRUNK;
-      else if (o.wgrad_mfma) wg = S3_WGRAD_F32_TRUNK;
-      v[S3_OPINFO_WGRAD] = wg;
-      int dg = S3_DGRAD_DIRECT;
-      if (o.dgrad_chunked) dg = S3_DGRAD_MFMA_CHUNKED;
-      else if (o.dgrad_fewch) dg = S3_DGRAD_FEWCH_FRAME;
-      else if (o.dgrad_valid) dg = S3_DGRAD_MFMA_VALID;
-      else if (o.dgrad_mfma) dg = S3_DGRAD_MFMA_FRAME;
-      else if (o.dgrad_s2) dg = S3_DGRAD_S2;
-      else if (o.dgrad_c2) dg = S3_DGRAD_C2;
-      else if (o.gconv_dgrad) dg = S3_DGRAD_GCONV;
-      else if (o.fewpos && o.fp_wt) dg = S3_DGRAD_FEWPOS;
-      v[S3_OPINFO_DGRAD] = dg;
+      v[S3_OPINFO_WGRAD] = wgrad_public(o.wgrad);
+      v[S3_OPINFO_DGRAD] = dgrad_public(o.dgrad);
       v[S3_OPINFO_DGRAD_FRAME16] = o.dgrad_frame16 ? 1 : 0;
       v[S3_OPINFO_MASK_FUSED_FROM] = o.mask_prod;
     }
@@ -1959,7 +2098,7 @@ static int window_op(const s3_plan* pl) {
   if (i < 0) return -1;
   const OpRec& o = pl->ops[i];
   if (o.d.kind != S3_OP_CONV || o.d.res >= 0 || o.cg.d2s != 1 || !o.io.in_bf16 || o.io.out_bf16) return -1;
-  if (conv_fwd_kind(pl, o) != S3_FWD_TAIL_MFMA) return -1;
+  if (o.fwd != Fwd::TAIL_MFMA) return -1;
   const int ro = root_of(pl, o.d.out);
   if (ro != root_of(pl, pl->output)) return -1;
   const TensorRec& ot = pl->t[ro];
@@ -2190,9 +2329,9 @@ static int plan_backward_impl(s3_plan* pl, const void* d_output, void* d_input, 
         if (only16) {
           dpre16 = pl->dpre16;
           pl->dpre16_for = -1;
-          const bool trunk16 = o.use16 && (o.wgrad_bf16 || (o.wgrad_bf16_2d && !o.fewpos && o.io.in_bf16 &&
-                                                            g.s[0] == 1 && (g.Cout & 3) == 0));
-          const bool fewch16 = o.wgrad_c2 && (o.dgrad_c2 || !wants_grad(d.in0));
+          const bool trunk16 = o.use16 && (o.wgrad == Wgrad::BF16_TRUNK ||
+                                           (o.wgrad == Wgrad::BF16_2D && o.io.in_bf16 && g.s[0] == 1 && (g.Cout & 3) == 0));
+          const bool fewch16 = o.wgrad == Wgrad::C2 && (dgrad_is_c2(o.dgrad) || !wants_grad(d.in0));
           if ((!trunk16 && !fewch16) || d.res >= 0)
             S3_FAIL(ctx, S3_ESTATE, "backward: bf16-only dPre reached a conv that needs fp32");
         } else if (pl->dpre16_for == ro && !pl->dpre16_only) {
@@ -2207,9 +2346,8 @@ static int plan_backward_impl(s3_plan* pl, const void* d_output, void* d_input, 
         float fp_slope = 0.f;
         // (both readers of dPre must be the one-launch kernels: the data gradient
         // of a fewpos conv may still run on another family)
-        const bool fp_dg = o.fewpos && o.fp_mfma && !o.dgrad_chunked && !o.dgrad_mfma && !o.dgrad_s2 &&
-                           !o.dgrad_c2 && !o.gconv_dgrad;
-        if (o.fewpos && o.fp_mfma && (fp_dg || !wants_grad(d.in0)) &&
+        const bool fp_dg = o.dgrad == Dgrad::FEWPOS_MFMA;
+        if (o.fam == Fam::FEWPOS_MFMA && (fp_dg || !wants_grad(d.in0)) &&
             g.d2s <= 1 && !o.io.out_bf16 && pl->t[ro].dtype == 0 &&
             (g.act == S3_ACT_LEAKY || g.act == S3_ACT_RELU) && !pl->premasked[ro] && !only16 &&
             !s3_opt_has(S3O_NO_MASK_FUSE)) {
@@ -2228,13 +2366,13 @@ static int plan_backward_impl(s3_plan* pl, const void* d_output, void* d_input, 
           // frame, bias gradient from the channel sums riding along: the
           // fp32 dPre (151 MB per trunk conv at C2 batch 8) is not written.
           const int64_t n_el = (int64_t)g.N * g.O[0] * g.O[1] * g.O[2] * g.Cout;
-          const bool wg16 = o.wgrad_bf16 && !o.fewpos && !o.wgrad_tail && !o.wgrad_c2 && !o.wgrad_bf16_2d &&
-                            !o.wgrad_bf16_gen && !o.wgrad_gen && o.io.in_bf16 && (g.Cout & 3) == 0;
-          const bool dg16 = o.dgrad_mfma && !o.dgrad_chunked && !o.dgrad_fewch && o.use16;
+          const bool wg16 = o.wgrad == Wgrad::BF16_TRUNK && o.io.in_bf16 && (g.Cout & 3) == 0;
+          const bool dg16 = (o.dgrad == Dgrad::MFMA_FRAME || o.dgrad == Dgrad::MFMA_VALID || o.dgrad == Dgrad::GEN) &&
+                            o.use16;
           // (64 -> C_out > 64 + depth-to-space: the slices of the chunked data
           // gradient read the bf16 copy when they run on the persistent kernel)
           const int nk16 = (g.Cout + 63) / 64;
-          const bool dgc16 = o.dgrad_chunked && o.use16 && side && (g.Cout & 7) == 0 &&
+          const bool dgc16 = dgrad_is_chunked(o.dgrad) && o.use16 && side && (g.Cout & 7) == 0 &&
                              conv_mfma_persist_dgrad_supported(ctx, conv_dgrad_chunk_geom(g, 0)) &&
                              conv_mfma_persist_dgrad_geom_ok(conv_dgrad_chunk_geom(g, nk16 - 1));
           const bool skip32 = side && pl->precision == S3_PREC_BF16 &&
@@ -2250,9 +2388,7 @@ static int plan_backward_impl(s3_plan* pl, const void* d_output, void* d_input, 
         }
         const int64_t npos = (int64_t)g.N * g.O[0] * g.O[1] * g.O[2];
         // few positions: the one-launch weight gradient leaves the bias gradient too
-        const bool fp_wg = dpre != nullptr &&
-                           ((o.fewpos && o.fp_mfma) || (o.fp_wg_mfma && !o.fewpos && !o.wgrad_tail && !o.wgrad_c2 && !o.wgrad_bf16_2d && !o.wgrad_bf16_gen &&
-                                         !o.wgrad_gen && !o.wgrad_bf16 && !o.wgrad_mfma && o.fewpos_wgrad && !o.io.in_bf16));
+        const bool fp_wg = dpre != nullptr && o.wgrad == Wgrad::FEWPOS_MFMA;
         // ... and when its data gradient is the one-launch kernel too, both go
         // out as ONE launch (at the data gradient's place below)
         const ConvGeom fp_gd = g.pad_mode == S3_PAD_REFLECT ? conv_fewpos_frame_geom(g) : g;
@@ -2279,8 +2415,7 @@ static int plan_backward_impl(s3_plan* pl, const void* d_output, void* d_input, 
         } else if (need_wgrad && !fp_both) {
           if (d.b >= 0) {
             // (its launch rides along the reduction of a bf16-family weight gradient)
-            const bool ride = !o.fewpos && !o.wgrad_tail && !o.wgrad_c2 &&
-                              (o.wgrad_bf16_2d || o.wgrad_bf16_gen || (!o.wgrad_gen && o.wgrad_bf16));
+            const bool ride = o.wgrad == Wgrad::BF16_2D || o.wgrad == Wgrad::BF16_GEN || o.wgrad == Wgrad::BF16_TRUNK;
             if (mask_sums)
               rc = launch_bias_grad_from_partial(ctx, pl->bsum2, conv_epilogue_bwd_blocks(ctx, g, true), g.Cout,
                                                  G + P->p[d.b].offset, accumulate_wgrad, ride);
@@ -2293,39 +2428,45 @@ static int plan_backward_impl(s3_plan* pl, const void* d_output, void* d_input, 
               rc = launch_bias_grad(ctx, dpre, npos, g.Cout, G + P->p[d.b].offset, accumulate_wgrad);
             if (rc) return rc;
           }
-          if (o.fewpos)
-            rc = launch_conv_fewpos_wgrad(ctx, g, tptr(pl, d.in0), dpre, G + P->p[d.w].offset, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad);
-          else if (o.wgrad_tail)
-            rc = launch_conv_wgrad_tail(ctx, g, tptr(pl, d.in0), dpre, G + P->p[d.w].offset, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad, o.io.in_bf16);
-          else if (o.wgrad_c2)
-            rc = launch_conv_wgrad_c2(ctx, g, tptr(pl, d.in0), only16 ? (const float*)dpre16 : dpre, G + P->p[d.w].offset,
-                                      pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad, only16 ? 1 : 0,
-                                      pl->precision == S3_PREC_BF16X3);
-          else if (o.wgrad_bf16_2d)
-          {
-            // (bf16-only dPre out of the consumer's masked fold, or a bf16 copy next to the fp32 one)
-            const bool dy16 = only16 || (dpre16 && o.io.in_bf16 && g.s[0] == 1 && (g.Cout & 3) == 0 && (g.Cin & 7) == 0);
-            rc = launch_conv_wgrad_bf16_2d(ctx, g, tptr(pl, d.in0), dy16 ? (const float*)dpre16 : dpre, G + P->p[d.w].offset,
-                                           pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad, o.io.in_bf16, dy16 ? 1 : 0);
+          float* dw = G + P->p[d.w].offset;
+          switch (o.wgrad) {
+            case Wgrad::FEWPOS_MFMA: case Wgrad::FEWPOS:
+              rc = launch_conv_fewpos_wgrad(ctx, g, tptr(pl, d.in0), dpre, dw, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad);
+              break;
+            case Wgrad::TAIL:
+              rc = launch_conv_wgrad_tail(ctx, g, tptr(pl, d.in0), dpre, dw, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad, o.io.in_bf16);
+              break;
+            case Wgrad::C2:
+              rc = launch_conv_wgrad_c2(ctx, g, tptr(pl, d.in0), only16 ? (const float*)dpre16 : dpre, dw,
+                                        pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad, only16 ? 1 : 0,
+                                        pl->precision == S3_PREC_BF16X3);
+              break;
+            case Wgrad::BF16_2D: {
+              // (bf16-only dPre out of the consumer's masked fold, or a bf16 copy next to the fp32 one)
+              const bool dy16 = only16 || (dpre16 && o.io.in_bf16 && g.s[0] == 1 && (g.Cout & 3) == 0 && (g.Cin & 7) == 0);
+              rc = launch_conv_wgrad_bf16_2d(ctx, g, tptr(pl, d.in0), dy16 ? (const float*)dpre16 : dpre, dw,
+                                             pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad, o.io.in_bf16, dy16 ? 1 : 0);
+            } break;
+            case Wgrad::BF16_GEN:
+              rc = launch_conv_wgrad_bf16_gen(ctx, g, tptr(pl, d.in0), dpre, dw, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad, o.io.in_bf16,
+                                              pl->precision == S3_PREC_BF16X3);
+              break;
+            case Wgrad::F32_GEN:
+              rc = launch_conv_wgrad_gen(ctx, g, tptr(pl, d.in0), dpre, dw, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad);
+              break;
+            case Wgrad::BF16_TRUNK: {
+              const bool dy16 = only16 || (dpre16 && o.io.in_bf16 && (g.Cout & 3) == 0);
+              rc = launch_conv_wgrad_bf16(ctx, g, tptr(pl, d.in0), dy16 ? (const float*)dpre16 : dpre, dw,
+                                          pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad, o.io.in_bf16, dy16 ? 1 : 0,
+                                          pl->precision == S3_PREC_BF16X3 ? 1 : 0);
+            } break;
+            case Wgrad::F32_TRUNK:
+              rc = launch_conv_wgrad_mfma(ctx, g, tptr(pl, d.in0), dpre, dw, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad);
+              break;
+            case Wgrad::DIRECT:
+              rc = launch_conv_generic_wgrad(ctx, g, tptr(pl, d.in0), dpre, dw, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad);
+              break;
           }
-          else if (o.wgrad_bf16_gen)
-            rc = launch_conv_wgrad_bf16_gen(ctx, g, tptr(pl, d.in0), dpre, G + P->p[d.w].offset, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad, o.io.in_bf16,
-                                            pl->precision == S3_PREC_BF16X3);
-          else if (o.wgrad_gen)
-            rc = launch_conv_wgrad_gen(ctx, g, tptr(pl, d.in0), dpre, G + P->p[d.w].offset, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad);
-          else if (o.wgrad_bf16)
-          {
-            const bool dy16 = only16 || (dpre16 && o.io.in_bf16 && (g.Cout & 3) == 0);
-            rc = launch_conv_wgrad_bf16(ctx, g, tptr(pl, d.in0), dy16 ? (const float*)dpre16 : dpre, G + P->p[d.w].offset,
-                                        pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad, o.io.in_bf16, dy16 ? 1 : 0,
-                                        pl->precision == S3_PREC_BF16X3 ? 1 : 0);
-          }
-          else if (o.wgrad_mfma)
-            rc = launch_conv_wgrad_mfma(ctx, g, tptr(pl, d.in0), dpre, G + P->p[d.w].offset, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad);
-          else if (o.fewpos_wgrad && !o.io.in_bf16)
-            rc = launch_conv_fewpos_wgrad(ctx, g, tptr(pl, d.in0), dpre, G + P->p[d.w].offset, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad);
-          else
-            rc = launch_conv_generic_wgrad(ctx, g, tptr(pl, d.in0), dpre, G + P->p[d.w].offset, pl->wg_partial, pl->wg_partial_bytes, accumulate_wgrad);
           if (rc) return rc;
           rc = s3_flush_pending_bias(ctx);     // (nothing took it along)
           if (rc) return rc;
@@ -2400,8 +2541,8 @@ static int plan_backward_impl(s3_plan* pl, const void* d_output, void* d_input, 
             // 151 MB and the readers stage half the bytes; they would round to
             // bf16 (the same round-to-nearest-even) anyway.
             const bool to16 = out == pl->t[rin].gptr && back_to_back(o.mask_prod, i) && po.use16 &&
-                              (po.wgrad_bf16 || (po.wgrad_bf16_2d && !po.fewpos && !po.wgrad_tail && !po.wgrad_c2 &&
-                                                 po.cg.s[0] == 1 && !s3_opt_has(S3O_NO_TRAIN2D_BF16))) &&
+                              (po.wgrad == Wgrad::BF16_TRUNK ||
+                               (po.wgrad == Wgrad::BF16_2D && po.cg.s[0] == 1 && !s3_opt_has(S3O_NO_TRAIN2D_BF16))) &&
                               po.io.in_bf16 && po.d.res < 0 &&
                               (po.cg.Cout & 3) == 0 && pl->dpre16 && pl->dpre16_for < 0 &&
                               (!need_wgrad || po.d.b < 0 || bs != nullptr) && pl->precision == S3_PREC_BF16;
@@ -2412,226 +2553,229 @@ static int plan_backward_impl(s3_plan* pl, const void* d_output, void* d_input, 
             if (!frc && to16) { pl->dpre16_for = rin; pl->dpre16_only = true; }
             return frc;
           };
-          if (o.dgrad_chunked) {
-            // 64-channel slices of dPre through the 64 -> 64 halo-tile kernel,
-            // accumulated in place over the padded frame, then the fold
-            const int nk = (g.Cout + 63) / 64;
-            if (o.dg_version != P->version) {
+          switch (o.dgrad) {
+            case Dgrad::CHUNKED_FRAME: case Dgrad::CHUNKED_VALID: {
+              // 64-channel slices of dPre through the 64 -> 64 halo-tile kernel,
+              // accumulated in place over the padded frame, then the fold
+              const int nk = (g.Cout + 63) / 64;
+              if (o.dg_version != P->version) {
+                for (int k = 0; k < nk; ++k) {
+                  rc = launch_conv_dgrad_chunk_pack(ctx, g, W + P->p[d.w].offset, o.dg_w32, k);
+                  if (!rc) rc = launch_conv_mfma_pack(ctx, conv_dgrad_chunk_geom(g, k), pl->precision, o.dg_w32, o.dgc_wbf[k]);
+                  if (rc) return rc;
+                }
+                o.dg_version = P->version;
+              }
+              float* acc_to = o.dgrad == Dgrad::CHUNKED_VALID ? dst : pl->dxp;   // valid padding: x's own grid
+              // with the bf16 copy of dPre: the slices go through the persistent
+              // kernel (stacked frames, the later slices add in its store)
+              const bool p16 = o.use16 && dpre16 && conv_mfma_persist_dgrad_supported(ctx, conv_dgrad_chunk_geom(g, 0)) &&
+                               conv_mfma_persist_dgrad_geom_ok(conv_dgrad_chunk_geom(g, nk - 1));
               for (int k = 0; k < nk; ++k) {
-                rc = launch_conv_dgrad_chunk_pack(ctx, g, W + P->p[d.w].offset, o.dg_w32, k);
-                if (!rc) rc = launch_conv_mfma_pack(ctx, conv_dgrad_chunk_geom(g, k), pl->precision, o.dg_w32, o.dgc_wbf[k]);
+                const ConvGeom cgk = conv_dgrad_chunk_geom(g, k);
+                if (p16)
+                  rc = launch_conv_mfma_persist_dgrad(ctx, cgk, (const unsigned short*)dpre16 + 64 * k,
+                                                      (const char*)o.dgc_wbf[k] + (size_t)27 * 64 * 64 * 2, acc_to, k ? 1 : 0);
+                else
+                  rc = launch_conv_mfma_fwd(ctx, cgk, pl->precision, dpre + 64 * k, o.dgc_wbf[k],
+                                            nullptr, k ? acc_to : nullptr, acc_to, ConvIO());
                 if (rc) return rc;
               }
-              o.dg_version = P->version;
-            }
-            float* acc_to = o.dgrad_valid ? dst : pl->dxp;   // valid padding: x's own grid
-            // with the bf16 copy of dPre: the slices go through the persistent
-            // kernel (stacked frames, the later slices add in its store)
-            const bool p16 = o.use16 && dpre16 && conv_mfma_persist_dgrad_supported(ctx, conv_dgrad_chunk_geom(g, 0)) &&
-                             conv_mfma_persist_dgrad_geom_ok(conv_dgrad_chunk_geom(g, nk - 1));
-            for (int k = 0; k < nk; ++k) {
-              const ConvGeom cgk = conv_dgrad_chunk_geom(g, k);
-              if (p16)
-                rc = launch_conv_mfma_persist_dgrad(ctx, cgk, (const unsigned short*)dpre16 + 64 * k,
-                                                    (const char*)o.dgc_wbf[k] + (size_t)27 * 64 * 64 * 2, acc_to, k ? 1 : 0);
-              else
-                rc = launch_conv_mfma_fwd(ctx, cgk, pl->precision, dpre + 64 * k, o.dgc_wbf[k],
-                                          nullptr, k ? acc_to : nullptr, acc_to, ConvIO());
-              if (rc) return rc;
-            }
-            if (o.dgrad_valid) {
-              rc = grad_deliver(pl, d.in0, dst);
-              if (rc) return rc;
-              break;
-            }
-            GatherGeom fg;
-            fg.kind = S3_OP_PAD; fg.N = g.N;
-            for (int q = 0; q < 3; ++q) { fg.Di[q] = g.D[q]; fg.Do[q] = g.D[q] + 2; fg.lo[q] = 1; }
-            fg.Ci = g.Cin; fg.Co = g.Cin; fg.pad_mode = g.pad_mode;
-            fg.rep = 1; fg.d2s = 1; fg.c_off = 0;
-            rc = fold_frame(fg, dst);
-          } else if (o.dgrad_mfma) {
-            // dXpad = conv_zero(dPre, flip(W)^T) over the padded frame, then
-            // the adjoint of the virtual padding folds the border back
-            if (o.dg_version != P->version) {
-              rc = launch_conv_dgrad_pack(ctx, g, W + P->p[d.w].offset, o.dg_w32);
-              if (!rc && o.dgrad_fewch)
-                rc = launch_gconv_pack(ctx, o.dg, o.dg_w32, o.dg_wbf, 0, pl->precision == S3_PREC_BF16X3);
-              else if (!rc && pl->precision != S3_PREC_F32)
-                rc = launch_conv_mfma_pack(ctx, o.dg, pl->precision, o.dg_w32, o.dg_wbf);
-              if (rc) return rc;
-              o.dg_version = P->version;
-            }
-            const void* wp = pl->precision != S3_PREC_F32 ? (const void*)o.dg_wbf : (const void*)o.dg_w32;
-            int frame16 = 0;
-            if (o.dgrad_fewch)
-              rc = launch_gconv_fwd(ctx, o.dg, dpre, o.dg_wbf, nullptr, nullptr, pl->dxp, 0, 0, pl->precision == S3_PREC_BF16X3);
-            else if (o.use16 && dpre16 && pl->precision == S3_PREC_BF16 &&
-                     conv_mfma_persist_dgrad_supported(ctx, o.dg)) {
-              // the persistent trunk kernel over the stacked frames (a valid conv's
-              // full correlation lands on x's own grid: straight into dst)
-              const size_t tile_img = (size_t)((o.dg.Cout + 63) / 64) * 27 * 64 * 64 * 2;
-              frame16 = o.dgrad_frame16;
-              rc = launch_conv_mfma_persist_dgrad(ctx, o.dg, dpre16, (const char*)o.dg_wbf + tile_img,
-                                                  o.dgrad_valid ? dst : pl->dxp, 0, frame16);
-            } else {
-              ConvIO dio;
-              dio.in_bf16 = (o.use16 && dpre16) ? 1 : 0;
-              // 2-D 64 -> 64 k convs: the frame form of the weights-stationary
-              // kernel, bf16 dPre in, bf16 frame out (folded from bf16)
-              if (dio.in_bf16 && o.dgrad_gen && o.dgrad_frame16 && !o.dgrad_valid && pl->precision == S3_PREC_BF16) {
-                ConvIO wio = dio;
-                wio.out_bf16 = 1;
-                if (conv2d_ws_supported(o.dg, pl->precision, wio, false)) { dio = wio; frame16 = 1; }
-              }
-              rc = launch_conv_mfma_fwd(ctx, o.dg, pl->precision, dio.in_bf16 ? dpre16 : (const void*)dpre, wp, nullptr,
-                                        nullptr, o.dgrad_valid ? dst : pl->dxp, dio);
-            }
-            if (rc) return rc;
-            if (o.dgrad_valid) {
-              rc = grad_deliver(pl, d.in0, dst);
-              if (rc) return rc;
-              break;
-            }
-            GatherGeom fg;
-            fg.kind = S3_OP_PAD; fg.N = g.N;
-            for (int q = 0; q < 3; ++q) {
-              const int pq = g.k[q] == 3 ? 1 : 0;      // (k = 1 axes of a 2-D conv carry no frame)
-              fg.Di[q] = g.D[q]; fg.Do[q] = g.D[q] + 2 * pq; fg.lo[q] = pq;
-            }
-            fg.Ci = g.Cin; fg.Co = g.Cin; fg.pad_mode = g.pad_mode;
-            fg.rep = 1; fg.d2s = 1; fg.c_off = 0;
-            rc = fold_frame(fg, dst, frame16);
-          } else if (o.dgrad_s2 && pl->precision == S3_PREC_BF16X3) {
-            if (o.dc2_version != (int64_t)P->version) {
-              rc = launch_conv_dgrad_s2_x3_pack(ctx, g, W + P->p[d.w].offset, o.dc2_w);
-              if (rc) return rc;
-              o.dc2_version = (int64_t)P->version;
-            }
-            const int rin = root_of(pl, d.in0);
-            const bool fuse = o.mask_prod >= 0 && !pl->gwritten[rin] && !s3_opt_has(S3O_NO_MASK_FUSE) &&
-                              pl->t[rin].dtype == 0;
-            const ConvGeom& pg = pl->ops[fuse ? o.mask_prod : i].cg;
-            rc = launch_conv_dgrad_s2_x3(ctx, g, dpre, o.dc2_w, dst, fuse ? (const float*)tptr(pl, d.in0) : nullptr,
-                                         pg.act == S3_ACT_LEAKY ? pg.alpha : 0.f);
-            if (!rc && fuse) pl->premasked[rin] = 1;
-          } else if (o.dgrad_s2) {
-            if (o.dc2_version != (int64_t)P->version) {
-              rc = launch_conv_dgrad_s2_pack(ctx, g, W + P->p[d.w].offset, o.dc2_w);
-              if (rc) return rc;
-              o.dc2_version = (int64_t)P->version;
-            }
-            // single consumer of an activated conv output: its LeakyReLU / ReLU
-            // adjoint is applied in the store (the producer then skips its mask pass)
-            const int rin = root_of(pl, d.in0);
-            const bool fuse = o.mask_prod >= 0 && !pl->gwritten[rin] && !s3_opt_has(S3O_NO_MASK_FUSE);
-            const OpRec& po = pl->ops[fuse ? o.mask_prod : i];
-            const ConvGeom& pg = po.cg;
-            // dx is dPre of the few-channel conv below (mask fused, single
-            // consumer).  Its weight gradient (conv_wgrad_c2_kernel), its data
-            // gradient (conv_dgrad_c2_kernel, generator step only) and its bias
-            // gradient (channel sums riding along here) all take bf16: store it
-            // as bf16 ONLY — 0.89 instead of 1.78 GB written here and read there,
-            // and no separate bias pass over it.
-            const int nblk = conv_dgrad_s2_blocks(g);
-            const bool sums = need_wgrad && po.d.b >= 0;
-            const bool to16 = fuse && back_to_back(o.mask_prod, i) && dst == pl->t[rin].gptr &&
-                              pl->precision == S3_PREC_BF16 && po.wgrad_c2 &&
-                              po.cg.Cin == 2 && po.cg.Cout == 32 && po.d.res < 0 &&
-                              (po.dgrad_c2 || !wants_grad(po.d.in0)) && conv_dgrad_s2_out16_ok(g) && pl->dpre16 &&
-                              pl->dpre16_bytes >= (size_t)pl->t[rin].numel * 2 && pl->dpre16_for < 0 &&
-                              (!sums || (pl->bsum && nblk <= 4096 && !s3_opt_has(S3O_NO_BIAS_FUSE))) &&
-                              !s3_opt_has(S3O_NO_DPRE16);
-            rc = launch_conv_dgrad_s2(ctx, g, dpre, o.dc2_w, to16 ? (float*)pl->dpre16 : dst,
-                                      fuse ? tptr(pl, d.in0) : nullptr, pg.act == S3_ACT_LEAKY ? pg.alpha : 0.f,
-                                      o.io.in_bf16, to16 ? 1 : 0, (to16 && sums) ? pl->bsum : nullptr,
-                                      (to16 && fuse && o.io.in_bf16) ? po.sign_bytes : nullptr);
-            if (!rc && fuse) pl->premasked[rin] = 1;
-            if (!rc && to16) {
-              pl->dpre16_for = rin; pl->dpre16_only = true;
-              if (sums) { pl->bsum_for = rin; pl->bsum_nblk = nblk; }
-            }
-          } else if (o.dgrad_c2 && pl->precision == S3_PREC_BF16X3) {
-            if (o.dc2_version != (int64_t)P->version) {
-              rc = launch_conv_dgrad_c2_x3_pack(ctx, g, W + P->p[d.w].offset, o.dc2_w);
-              if (rc) return rc;
-              o.dc2_version = (int64_t)P->version;
-            }
-            rc = launch_conv_dgrad_c2_x3(ctx, g, dpre, o.dc2_w, dst);
-          } else if (o.dgrad_c2) {
-            if (o.dc2_version != (int64_t)P->version) {
-              rc = launch_conv_dgrad_c2_pack(ctx, g, W + P->p[d.w].offset, o.dc2_w);
-              if (rc) return rc;
-              o.dc2_version = (int64_t)P->version;
-            }
-            rc = launch_conv_dgrad_c2(ctx, g, only16 ? (const float*)dpre16 : dpre, o.dc2_w, dst, only16 ? 1 : 0);
-          } else if (o.gconv_dgrad) {
-            if (o.gct_version != P->version) {
-              rc = launch_gconv_pack(ctx, g, W + P->p[d.w].offset, o.gc_wt, 1, pl->precision == S3_PREC_BF16X3);
-              if (rc) return rc;
-              o.gct_version = P->version;
-            }
-            if (g.pad_mode == S3_PAD_REFLECT) {
-              // dXpad over the reflect-padded frame, then fold the border back
-              rc = launch_gconv_dgrad(ctx, g, dpre, o.gc_wt, pl->dxp, 0, 1, 0, pl->precision == S3_PREC_BF16X3);
-              if (rc) return rc;
+              if (o.dgrad == Dgrad::CHUNKED_VALID) break;   // (x's own grid: no fold)
               GatherGeom fg;
               fg.kind = S3_OP_PAD; fg.N = g.N;
-              for (int q = 0; q < 3; ++q) { fg.Di[q] = g.D[q]; fg.Do[q] = g.D[q] + 2 * g.lo[q]; fg.lo[q] = g.lo[q]; }
+              for (int q = 0; q < 3; ++q) { fg.Di[q] = g.D[q]; fg.Do[q] = g.D[q] + 2; fg.lo[q] = 1; }
               fg.Ci = g.Cin; fg.Co = g.Cin; fg.pad_mode = g.pad_mode;
               fg.rep = 1; fg.d2s = 1; fg.c_off = 0;
-              rc = launch_gather_bwd(ctx, fg, pl->dxp, dst);
-            } else {
-              const bool dy16 = o.use16 && dpre16 != nullptr;
-              rc = launch_gconv_dgrad(ctx, g, dy16 ? (const float*)dpre16 : dpre, o.gc_wt, dst, 0, 0, dy16 ? 1 : 0,
-                                      pl->precision == S3_PREC_BF16X3);
-            }
-          } else if (o.fewpos && o.fp_mfma) {
-            // (reads the [tap][ci][co] filter along co: no transposed copy)
-            const float* wf = W + P->p[d.w].offset;
-            const bool reflect = g.pad_mode == S3_PAD_REFLECT;
-            if (fp_both) {
-              rc = launch_conv_fewpos_bwd_mfma(ctx, g, fp_gd, tptr(pl, d.in0), dpre, wf, reflect ? pl->dxp : dst,
-                                               G + P->p[d.w].offset, d.b >= 0 ? G + P->p[d.b].offset : nullptr,
-                                               accumulate_wgrad, fp_mask_y, fp_slope);
-              if (rc) return rc;
-            }
-            if (reflect) {
-              if (!fp_both)
-                rc = launch_conv_fewpos_mfma(ctx, fp_gd, 1, dpre, wf, nullptr, nullptr, pl->dxp, fp_mask_y, fp_slope);
-              if (rc) return rc;
-              GatherGeom fg;
-              fg.kind = S3_OP_PAD; fg.N = g.N;
-              for (int q = 0; q < 3; ++q) { fg.Di[q] = g.D[q]; fg.Do[q] = g.D[q] + 2 * g.lo[q]; fg.lo[q] = g.lo[q]; }
-              fg.Ci = g.Cin; fg.Co = g.Cin; fg.pad_mode = g.pad_mode;
-              fg.rep = 1; fg.d2s = 1; fg.c_off = 0;
-              // (with the producer's activation adjoint, or the first contribution
-              // of a skip tensor, in the same store: no mask pass, no axpy)
               rc = fold_frame(fg, dst);
-            } else if (!fp_both) {
-              rc = launch_conv_fewpos_mfma(ctx, g, 1, dpre, wf, nullptr, nullptr, dst, fp_mask_y, fp_slope);
-            }
-          } else if (o.fewpos && o.fp_wt) {
-            if (o.fp_version != P->version) {
-              rc = launch_conv_fewpos_transpose(ctx, g, W + P->p[d.w].offset, o.fp_wt);
+            } break;
+            case Dgrad::MFMA_FRAME: case Dgrad::MFMA_VALID: case Dgrad::GEN: case Dgrad::FEWCH: {
+              // dXpad = conv_zero(dPre, flip(W)^T) over the padded frame, then
+              // the adjoint of the virtual padding folds the border back
+              if (o.dg_version != P->version) {
+                rc = launch_conv_dgrad_pack(ctx, g, W + P->p[d.w].offset, o.dg_w32);
+                if (!rc && o.dgrad == Dgrad::FEWCH)
+                  rc = launch_gconv_pack(ctx, o.dg, o.dg_w32, o.dg_wbf, 0, pl->precision == S3_PREC_BF16X3);
+                else if (!rc && pl->precision != S3_PREC_F32)
+                  rc = launch_conv_mfma_pack(ctx, o.dg, pl->precision, o.dg_w32, o.dg_wbf);
+                if (rc) return rc;
+                o.dg_version = P->version;
+              }
+              const void* wp = pl->precision != S3_PREC_F32 ? (const void*)o.dg_wbf : (const void*)o.dg_w32;
+              int frame16 = 0;
+              if (o.dgrad == Dgrad::FEWCH)
+                rc = launch_gconv_fwd(ctx, o.dg, dpre, o.dg_wbf, nullptr, nullptr, pl->dxp, 0, 0, pl->precision == S3_PREC_BF16X3);
+              else if (o.use16 && dpre16 && pl->precision == S3_PREC_BF16 &&
+                       conv_mfma_persist_dgrad_supported(ctx, o.dg)) {
+                // the persistent trunk kernel over the stacked frames (a valid conv's
+                // full correlation lands on x's own grid: straight into dst)
+                const size_t tile_img = (size_t)((o.dg.Cout + 63) / 64) * 27 * 64 * 64 * 2;
+                frame16 = o.dgrad_frame16;
+                rc = launch_conv_mfma_persist_dgrad(ctx, o.dg, dpre16, (const char*)o.dg_wbf + tile_img,
+                                                    o.dgrad == Dgrad::MFMA_VALID ? dst : pl->dxp, 0, frame16);
+              } else {
+                ConvIO dio;
+                dio.in_bf16 = (o.use16 && dpre16) ? 1 : 0;
+                // 2-D 64 -> 64 k convs: the frame form of the weights-stationary
+                // kernel, bf16 dPre in, bf16 frame out (folded from bf16)
+                if (dio.in_bf16 && o.dgrad == Dgrad::GEN && o.dgrad_frame16 && pl->precision == S3_PREC_BF16) {
+                  ConvIO wio = dio;
+                  wio.out_bf16 = 1;
+                  if (conv2d_ws_supported(o.dg, pl->precision, wio, false)) { dio = wio; frame16 = 1; }
+                }
+                rc = launch_conv_mfma_fwd(ctx, o.dg, pl->precision, dio.in_bf16 ? dpre16 : (const void*)dpre, wp, nullptr,
+                                          nullptr, o.dgrad == Dgrad::MFMA_VALID ? dst : pl->dxp, dio);
+              }
               if (rc) return rc;
-              o.fp_version = P->version;
-            }
-            if (g.pad_mode == S3_PAD_REFLECT) {
-              // dXpad over the padded frame (zero boundary), then fold the border back
-              rc = launch_conv_fewpos_dgrad(ctx, conv_fewpos_frame_geom(g), dpre, o.fp_wt, pl->dxp, pl->fp_partial, pl->fp_partial_bytes);
-              if (rc) return rc;
+              if (o.dgrad == Dgrad::MFMA_VALID) break;   // (x's own grid: no fold)
               GatherGeom fg;
               fg.kind = S3_OP_PAD; fg.N = g.N;
-              for (int q = 0; q < 3; ++q) { fg.Di[q] = g.D[q]; fg.Do[q] = g.D[q] + 2 * g.lo[q]; fg.lo[q] = g.lo[q]; }
+              for (int q = 0; q < 3; ++q) {
+                const int pq = g.k[q] == 3 ? 1 : 0;      // (k = 1 axes of a 2-D conv carry no frame)
+                fg.Di[q] = g.D[q]; fg.Do[q] = g.D[q] + 2 * pq; fg.lo[q] = pq;
+              }
               fg.Ci = g.Cin; fg.Co = g.Cin; fg.pad_mode = g.pad_mode;
               fg.rep = 1; fg.d2s = 1; fg.c_off = 0;
-              rc = launch_gather_bwd(ctx, fg, pl->dxp, dst);
-            } else {
-              rc = launch_conv_fewpos_dgrad(ctx, g, dpre, o.fp_wt, dst, pl->fp_partial, pl->fp_partial_bytes);
-            }
-          } else {
-            rc = launch_conv_generic_dgrad(ctx, g, dpre, W + P->p[d.w].offset, dst);
+              rc = fold_frame(fg, dst, frame16);
+            } break;
+            case Dgrad::S2_X3: {
+              if (o.dc2_version != (int64_t)P->version) {
+                rc = launch_conv_dgrad_s2_x3_pack(ctx, g, W + P->p[d.w].offset, o.dc2_w);
+                if (rc) return rc;
+                o.dc2_version = (int64_t)P->version;
+              }
+              const int rin = root_of(pl, d.in0);
+              const bool fuse = o.mask_prod >= 0 && !pl->gwritten[rin] && !s3_opt_has(S3O_NO_MASK_FUSE) &&
+                                pl->t[rin].dtype == 0;
+              const ConvGeom& pg = pl->ops[fuse ? o.mask_prod : i].cg;
+              rc = launch_conv_dgrad_s2_x3(ctx, g, dpre, o.dc2_w, dst, fuse ? (const float*)tptr(pl, d.in0) : nullptr,
+                                           pg.act == S3_ACT_LEAKY ? pg.alpha : 0.f);
+              if (!rc && fuse) pl->premasked[rin] = 1;
+            } break;
+            case Dgrad::S2: {
+              if (o.dc2_version != (int64_t)P->version) {
+                rc = launch_conv_dgrad_s2_pack(ctx, g, W + P->p[d.w].offset, o.dc2_w);
+                if (rc) return rc;
+                o.dc2_version = (int64_t)P->version;
+              }
+              // single consumer of an activated conv output: its LeakyReLU / ReLU
+              // adjoint is applied in the store (the producer then skips its mask pass)
+              const int rin = root_of(pl, d.in0);
+              const bool fuse = o.mask_prod >= 0 && !pl->gwritten[rin] && !s3_opt_has(S3O_NO_MASK_FUSE);
+              const OpRec& po = pl->ops[fuse ? o.mask_prod : i];
+              const ConvGeom& pg = po.cg;
+              // dx is dPre of the few-channel conv below (mask fused, single
+              // consumer).  Its weight gradient (conv_wgrad_c2_kernel), its data
+              // gradient (conv_dgrad_c2_kernel, generator step only) and its bias
+              // gradient (channel sums riding along here) all take bf16: store it
+              // as bf16 ONLY — 0.89 instead of 1.78 GB written here and read there,
+              // and no separate bias pass over it.
+              const int nblk = conv_dgrad_s2_blocks(g);
+              const bool sums = need_wgrad && po.d.b >= 0;
+              const bool to16 = fuse && back_to_back(o.mask_prod, i) && dst == pl->t[rin].gptr &&
+                                pl->precision == S3_PREC_BF16 && po.wgrad == Wgrad::C2 &&
+                                po.cg.Cin == 2 && po.cg.Cout == 32 && po.d.res < 0 &&
+                                (dgrad_is_c2(po.dgrad) || !wants_grad(po.d.in0)) && conv_dgrad_s2_out16_ok(g) && pl->dpre16 &&
+                                pl->dpre16_bytes >= (size_t)pl->t[rin].numel * 2 && pl->dpre16_for < 0 &&
+                                (!sums || (pl->bsum && nblk <= 4096 && !s3_opt_has(S3O_NO_BIAS_FUSE))) &&
+                                !s3_opt_has(S3O_NO_DPRE16);
+              rc = launch_conv_dgrad_s2(ctx, g, dpre, o.dc2_w, to16 ? (float*)pl->dpre16 : dst,
+                                        fuse ? tptr(pl, d.in0) : nullptr, pg.act == S3_ACT_LEAKY ? pg.alpha : 0.f,
+                                        o.io.in_bf16, to16 ? 1 : 0, (to16 && sums) ? pl->bsum : nullptr,
+                                        (to16 && fuse && o.io.in_bf16) ? po.sign_bytes : nullptr);
+              if (!rc && fuse) pl->premasked[rin] = 1;
+              if (!rc && to16) {
+                pl->dpre16_for = rin; pl->dpre16_only = true;
+                if (sums) { pl->bsum_for = rin; pl->bsum_nblk = nblk; }
+              }
+            } break;
+            case Dgrad::C2_X3: {
+              if (o.dc2_version != (int64_t)P->version) {
+                rc = launch_conv_dgrad_c2_x3_pack(ctx, g, W + P->p[d.w].offset, o.dc2_w);
+                if (rc) return rc;
+                o.dc2_version = (int64_t)P->version;
+              }
+              rc = launch_conv_dgrad_c2_x3(ctx, g, dpre, o.dc2_w, dst);
+            } break;
+            case Dgrad::C2: {
+              if (o.dc2_version != (int64_t)P->version) {
+                rc = launch_conv_dgrad_c2_pack(ctx, g, W + P->p[d.w].offset, o.dc2_w);
+                if (rc) return rc;
+                o.dc2_version = (int64_t)P->version;
+              }
+              rc = launch_conv_dgrad_c2(ctx, g, only16 ? (const float*)dpre16 : dpre, o.dc2_w, dst, only16 ? 1 : 0);
+            } break;
+            case Dgrad::GCONV: {
+              if (o.gct_version != P->version) {
+                rc = launch_gconv_pack(ctx, g, W + P->p[d.w].offset, o.gc_wt, 1, pl->precision == S3_PREC_BF16X3);
+                if (rc) return rc;
+                o.gct_version = P->version;
+              }
+              if (g.pad_mode == S3_PAD_REFLECT) {
+                // dXpad over the reflect-padded frame, then fold the border back
+                rc = launch_gconv_dgrad(ctx, g, dpre, o.gc_wt, pl->dxp, 0, 1, 0, pl->precision == S3_PREC_BF16X3);
+                if (rc) return rc;
+                GatherGeom fg;
+                fg.kind = S3_OP_PAD; fg.N = g.N;
+                for (int q = 0; q < 3; ++q) { fg.Di[q] = g.D[q]; fg.Do[q] = g.D[q] + 2 * g.lo[q]; fg.lo[q] = g.lo[q]; }
+                fg.Ci = g.Cin; fg.Co = g.Cin; fg.pad_mode = g.pad_mode;
+                fg.rep = 1; fg.d2s = 1; fg.c_off = 0;
+                rc = launch_gather_bwd(ctx, fg, pl->dxp, dst);
+              } else {
+                const bool dy16 = o.use16 && dpre16 != nullptr;
+                rc = launch_gconv_dgrad(ctx, g, dy16 ? (const float*)dpre16 : dpre, o.gc_wt, dst, 0, 0, dy16 ? 1 : 0,
+                                        pl->precision == S3_PREC_BF16X3);
+              }
+            } break;
+            case Dgrad::FEWPOS_MFMA: {
+              // (reads the [tap][ci][co] filter along co: no transposed copy)
+              const float* wf = W + P->p[d.w].offset;
+              const bool reflect = g.pad_mode == S3_PAD_REFLECT;
+              if (fp_both) {
+                rc = launch_conv_fewpos_bwd_mfma(ctx, g, fp_gd, tptr(pl, d.in0), dpre, wf, reflect ? pl->dxp : dst,
+                                                 G + P->p[d.w].offset, d.b >= 0 ? G + P->p[d.b].offset : nullptr,
+                                                 accumulate_wgrad, fp_mask_y, fp_slope);
+                if (rc) return rc;
+              }
+              if (reflect) {
+                if (!fp_both)
+                  rc = launch_conv_fewpos_mfma(ctx, fp_gd, 1, dpre, wf, nullptr, nullptr, pl->dxp, fp_mask_y, fp_slope);
+                if (rc) return rc;
+                GatherGeom fg;
+                fg.kind = S3_OP_PAD; fg.N = g.N;
+                for (int q = 0; q < 3; ++q) { fg.Di[q] = g.D[q]; fg.Do[q] = g.D[q] + 2 * g.lo[q]; fg.lo[q] = g.lo[q]; }
+                fg.Ci = g.Cin; fg.Co = g.Cin; fg.pad_mode = g.pad_mode;
+                fg.rep = 1; fg.d2s = 1; fg.c_off = 0;
+                // (with the producer's activation adjoint, or the first contribution
+                // of a skip tensor, in the same store: no mask pass, no axpy)
+                rc = fold_frame(fg, dst);
+              } else if (!fp_both) {
+                rc = launch_conv_fewpos_mfma(ctx, g, 1, dpre, wf, nullptr, nullptr, dst, fp_mask_y, fp_slope);
+              }
+            } break;
+            case Dgrad::FEWPOS: {
+              if (o.fp_version != P->version) {
+                rc = launch_conv_fewpos_transpose(ctx, g, W + P->p[d.w].offset, o.fp_wt);
+                if (rc) return rc;
+                o.fp_version = P->version;
+              }
+              if (g.pad_mode == S3_PAD_REFLECT) {
+                // dXpad over the padded frame (zero boundary), then fold the border back
+                rc = launch_conv_fewpos_dgrad(ctx, conv_fewpos_frame_geom(g), dpre, o.fp_wt, pl->dxp, pl->fp_partial, pl->fp_partial_bytes);
+                if (rc) return rc;
+                GatherGeom fg;
+                fg.kind = S3_OP_PAD; fg.N = g.N;
+                for (int q = 0; q < 3; ++q) { fg.Di[q] = g.D[q]; fg.Do[q] = g.D[q] + 2 * g.lo[q]; fg.lo[q] = g.lo[q]; }
+                fg.Ci = g.Cin; fg.Co = g.Cin; fg.pad_mode = g.pad_mode;
+                fg.rep = 1; fg.d2s = 1; fg.c_off = 0;
+                rc = launch_gather_bwd(ctx, fg, pl->dxp, dst);
+              } else {
+                rc = launch_conv_fewpos_dgrad(ctx, g, dpre, o.fp_wt, dst, pl->fp_partial, pl->fp_partial_bytes);
+              }
+            } break;
+            case Dgrad::DIRECT:
+              rc = launch_conv_generic_dgrad(ctx, g, dpre, W + P->p[d.w].offset, dst);
+              break;
           }
           if (rc) return rc;
           rc = grad_deliver(pl, d.in0, dst);
