@@ -571,6 +571,63 @@ int s3_gaussian_smooth(s3_ctx* ctx, const float* x, int n, int s1, int s2, int t
                        int c, const float* weights_host, int radius,
                        unsigned channel_mask, float* tmp, float* y);
 
+/* ---- non-neural downscalers on the device ------------
+ * replaces the host scipy / Pillow of the reference's LinearInterp and
+ * SurfaceSpatialMetModel (sup3r/models/linear.py, sup3r/models/surface.py):
+ *   s3_st_interp         = st_interp (sup3r/models/utilities.py:161-212) of
+ *                          every (obs, feature) field of LinearInterp.generate
+ *                          (linear.py:124-171): x (n, s1, s2, t, c) -> y (n,
+ *                          s1 s, s2 s, t t_enhance, c), trilinear with linear
+ *                          extrapolation.  axes = device table: int32 source
+ *                          index i0 of every output index of the three axes
+ *                          (s1 s, s2 s, t t_enhance in that order), then their
+ *                          fp32 fractions (host float64).  Axes of length 1
+ *                          are refused, as the reference asserts.
+ *   s3_resize2d          = PIL.Image.resize in mode 'F' of every (n, :, :, c)
+ *                          plane (downscale_arr, surface.py:286-318, without
+ *                          the bias fix): x (n, h, w, c) -> y (n, h s, w s, c),
+ *                          c <= 32.  tab_h / tab_w = device coefficient tables
+ *                          of the two axes (int32 lo[O], int32 cnt[O], fp32
+ *                          w[O][k]: Pillow's precompute_coeffs, host float64);
+ *                          lo_h_host / cnt_h_host = the host copy of the h
+ *                          axis' lo / cnt (tile geometry); planes = scratch of
+ *                          (3 c + 1) n h w floats.
+ *   s3_surface_downscale = SurfaceSpatialMetModel.generate (surface.py:
+ *                          578-713) on the whole batch: channel kinds
+ *                          S3_SURF_*, pair_host[i] = the temperature channel
+ *                          of humidity channel i (_get_temp_rh_ind, :212-248),
+ *                          consts_host = {temp_lapse, w_delta_temp,
+ *                          w_delta_topo, pres_div, pres_exp}, fix_bias
+ *                          (fix_downscaled_bias, :250-284: hr -= R(C(hr) -
+ *                          lr)), noise_host[c] = stdev of the uniform [0,
+ *                          stdev) noise added to channel c (0: none; null: no
+ *                          noise; Philox4x32-10 keyed by seed, counter (pixel,
+ *                          channel, call)).  topo_lr (h, w) and topo_hr (h s,
+ *                          w s) device fp32; g_hr = scratch of h s w s floats
+ *                          (needed with pressure channels).  The high-res
+ *                          field is written once (three launches with the bias
+ *                          fix).  min_pres_host (optional): receives the
+ *                          minimum of the final pressure channels before the
+ *                          noise (+inf without any); the call then waits for
+ *                          the stream. */
+#define S3_SURF_OTHER 0
+#define S3_SURF_TEMP 1
+#define S3_SURF_PRES 2
+#define S3_SURF_RH 3
+int s3_st_interp(s3_ctx* ctx, const float* x, int n, int s1, int s2, int t, int c,
+                 int s_enhance, int t_enhance, const void* axes, float* y);
+int s3_resize2d(s3_ctx* ctx, const float* x, int n, int h, int w, int c, int s_enhance,
+                const void* tab_h, const void* tab_w, const int* lo_h_host,
+                const int* cnt_h_host, int k, float* planes, float* y);
+int s3_surface_downscale(s3_ctx* ctx, const float* x, int n, int h, int w, int c,
+                         int s_enhance, const void* tab_h, const void* tab_w,
+                         const int* lo_h_host, const int* cnt_h_host, int k,
+                         const int* kinds_host, const int* pair_host,
+                         const float* consts_host, int fix_bias,
+                         const float* noise_host, uint64_t seed, uint32_t call,
+                         const float* topo_lr, const float* topo_hr, float* planes,
+                         float* g_hr, float* y, float* min_pres_host);
+
 /* ---- output epilogue on the device ----------------------
  * replaces the host numpy of OutputHandler._transform_output
  * (sup3r/writers/base.py:304-345) on a hi-res chunk (s1*s2, t, c) fp32:

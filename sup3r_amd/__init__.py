@@ -17,10 +17,13 @@ from .solar_cc import SolarCC  # noqa: E402,F401
 from .with_obs import Sup3rGanWithObs  # noqa: E402,F401
 from .forward_pass import (ChunkPathOptions, ChunkSlicer,  # noqa: E402,F401
                            ForwardPass)
-from .multi_step import MultiStepGan  # noqa: E402,F401
+from .multi_step import MultiStepGan, MultiStepSurfaceMetGan  # noqa: E402,F401
+from .linear import LinearInterp  # noqa: E402,F401
+from .surface import SurfaceSpatialMetModel  # noqa: E402,F401
 from .batch_queue import (DeviceBatchHandler, DeviceBatchQueue,  # noqa: E402,F401
                           DsetTuple)
 
-__all__ = ['Sup3rGan', 'Sup3rCondMom', 'Sup3rGanDC', 'SolarCC', 'Sup3rGanWithObs', 'MultiStepGan', 'ForwardPass', 'ChunkPathOptions',
+__all__ = ['Sup3rGan', 'Sup3rCondMom', 'Sup3rGanDC', 'SolarCC', 'Sup3rGanWithObs', 'MultiStepGan',
+           'MultiStepSurfaceMetGan', 'LinearInterp', 'SurfaceSpatialMetModel', 'ForwardPass', 'ChunkPathOptions',
            'ChunkSlicer', 'DeviceBatchQueue', 'DeviceBatchHandler', 'DsetTuple',
            '__version__']

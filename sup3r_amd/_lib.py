@@ -17,6 +17,7 @@ PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
 LOSS_MAE, LOSS_MSE, LOSS_EXP = 0, 1, 2
 BUF_W, BUF_G, BUF_M, BUF_V = 0, 1, 2, 3
 OPT_ADAM = 0
+SURF_OTHER, SURF_TEMP, SURF_PRES, SURF_RH = 0, 1, 2, 3
 E_TIMEOUT = -6
 PRECISIONS = {'f32': PREC_F32, 'bf16': PREC_BF16, 'bf16x3': PREC_BF16X3}
 
@@ -42,6 +43,7 @@ EXPORTS = [
     's3_specmap',
     's3_copy_channels', 's3_affine_channels', 's3_fill', 's3_copy_block',
     's3_coarsen', 's3_gaussian_smooth', 's3_chunk_stats',
+    's3_st_interp', 's3_resize2d', 's3_surface_downscale',
     's3_chunk_epilogue', 's3_chunk_time_last', 's3_chunk_time_first',
     's3_step_handover', 's3_broadcast_axis',
     's3_host_register', 's3_host_unregister', 's3_d2h_window',
@@ -213,6 +215,13 @@ def lib():
                              vp]),
         's3_gaussian_smooth': (i32, [vp, vp, i32, i32, i32, i32, i32, pf, i32,
                                      C.c_uint32, vp, vp]),
+        's3_st_interp': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp,
+                               vp]),
+        's3_resize2d': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp,
+                              i32, vp, vp]),
+        's3_surface_downscale': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp,
+                                       vp, vp, i32, vp, vp, vp, i32, vp, u64,
+                                       C.c_uint32, vp, vp, vp, vp, vp, vp]),
         's3_comm_unique_id': (i32, [vp]),
         's3_comm_init': (i32, [vp, i32, i32, vp]),
         's3_params_allreduce_grads': (i32, [vp]),

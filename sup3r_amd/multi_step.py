@@ -139,3 +139,37 @@ class MultiStepGan:
                     f'step {i + 1} of {last + 1} ({type(model).__name__}) '
                     f'failed on an array of shape {arr.shape}') from e
         return arr
+
+
+class MultiStepSurfaceMetGan(MultiStepGan):
+    """A spatial-only surface step (``SurfaceSpatialMetModel``) on a 4-D stack
+    of near-surface fields, then a (spatio)temporal model on the 5-D sample
+    whose time axis is that stack (sup3r/models/multi_step.py:340-482).  The
+    hand-over is ``_as_model_rank``'s (n, s1, s2, f) -> (1, s1, s2, n, f)."""
+
+    def generate(self, low_res, norm_in=True, un_norm_out=True,
+                 exogenous_data=None):
+        """``MultiStepGan.generate`` after checking that ``exogenous_data``
+        carries the two topography steps (low-res, high-res) of the surface
+        step: a bare ``AssertionError`` otherwise, before any step runs."""
+        msg = ('MultiStepSurfaceMetGan needs exogenous_data with two '
+               'topography steps, for low and high res topography inputs.')
+        exo_check = (exogenous_data is not None and
+                     len(exogenous_data['topography']['steps']) == 2)
+        assert exo_check, msg
+        return super().generate(low_res, norm_in, un_norm_out, exogenous_data)
+
+    @classmethod
+    def load(cls, surface_model_class='SurfaceSpatialMetModel',
+             temporal_model_class='MultiStepGan', surface_model_kwargs=None,
+             temporal_model_kwargs=None, verbose=True):
+        """the two models by class name from this package,
+        ``Class.load(verbose=verbose, **kwargs)`` each, chained"""
+        import sup3r_amd
+        s_models = getattr(sup3r_amd, surface_model_class).load(
+            verbose=verbose, **(surface_model_kwargs or {}))
+        t_models = getattr(sup3r_amd, temporal_model_class).load(
+            verbose=verbose, **(temporal_model_kwargs or {}))
+        s_models = getattr(s_models, 'models', [s_models])
+        t_models = getattr(t_models, 'models', [t_models])
+        return cls([*s_models, *t_models])
