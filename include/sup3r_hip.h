@@ -571,6 +571,46 @@ int s3_gaussian_smooth(s3_ctx* ctx, const float* x, int n, int s1, int s2, int t
                        int c, const float* weights_host, int radius,
                        unsigned channel_mask, float* tmp, float* y);
 
+/* ---- conditional-moment training targets on the device ---------------------
+ * replaces the host numpy / scipy of ConditionalBatchQueue.post_proc
+ * (sup3r/preprocessing/batch_queues/conditional.py:151-166): make_output of
+ * QueueMom1SF / Mom2 / Mom2Sep / Mom2SF / Mom2SepSF (:178-288) and make_mask
+ * (:79-127) in one streaming pass over the hi-res batch.
+ *   hr   (n, s1, s2, t, c_hr) fp32 (4-D batches: t = 1)
+ *   lr   (n, s1/s_enhance, s2/s_enhance, t/t_enhance, c_lr); read only with
+ *        S3_CM_SUBFILTER.  lr_channel_host[c] (host, c_hr entries) = the lr
+ *        channel of hr channel c (enhanced_lr[..., hr_features_ind])
+ *   mom1 (n, s1, s2, t, c_m), c_m <= c_hr: the first-moment model's output;
+ *        read only with S3_CM_MOM1.  For c >= c_m the first moment IS
+ *        hr[..., c] (_combine_loss_input, abstract.py:438-459: the truth's
+ *        exogenous channels stand in; the joined tensor is never written)
+ *   out[e] = v, with v = hr[e]; v -= e^ (S3_CM_SUBFILTER); v -= m (S3_CM_MOM1);
+ *        v *= v (S3_CM_SQUARE) — in this order, one fp32 rounding each.
+ *        e^ = lr cell (i / s, j / s, k / t_enhance)
+ *        (spatial_simple_enhancing / temporal_simple_enhancing mode
+ *        'constant', batch_queues/utilities.py:12-54, :106-173: zoom(order=0)
+ *        is a repeat); with S3_CM_LINEAR and t_enhance > 1 in time
+ *        lo + (hi - lo) * frac, i0 = min(k / t_enhance, t / t_enhance - 2),
+ *        frac = (k - i0 t_enhance) / t_enhance (interp1d(fill_value=
+ *        'extrapolate') over the landmarks 0, t_enhance, 2 t_enhance, ...).
+ *        t_enhance <= 1 ignores S3_CM_LINEAR, as the reference does.
+ *   mask[e] = 1 for s_pad <= i < s1 - s_pad, s_pad <= j < s2 - s_pad,
+ *        t_lo <= k < t_hi (every channel), else 0.
+ *   out == NULL or mask == NULL: that tensor is not written (not both).
+ * S3_EINVAL: extents that the enhancement factors do not divide, c_m > c_hr,
+ * a channel-map entry outside [0, c_lr), S3_CM_LINEAR with t_enhance > 1 and
+ * fewer than two low-res time steps (scipy returns NaN there), c_hr > 32,
+ * 2^31 or more elements. */
+#define S3_CM_SUBFILTER 1u
+#define S3_CM_LINEAR 2u
+#define S3_CM_MOM1 4u
+#define S3_CM_SQUARE 8u
+int s3_condmom_target(s3_ctx* ctx, const float* hr, const float* lr, const float* mom1,
+                      int n, int s1, int s2, int t, int c_hr, int c_lr, int c_m,
+                      const int* lr_channel_host, int s_enhance, int t_enhance,
+                      unsigned flags, int s_pad, int t_lo, int t_hi, float* out,
+                      float* mask);
+
 /* ---- non-neural downscalers on the device ------------
  * replaces the host scipy / Pillow of the reference's LinearInterp and
  * SurfaceSpatialMetModel (sup3r/models/linear.py, sup3r/models/surface.py):

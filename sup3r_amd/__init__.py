@@ -22,8 +22,10 @@ from .linear import LinearInterp  # noqa: E402,F401
 from .surface import SurfaceSpatialMetModel  # noqa: E402,F401
 from .batch_queue import (DeviceBatchHandler, DeviceBatchQueue,  # noqa: E402,F401
                           DsetTuple)
+from . import batch_queue_conditional as _cond  # noqa: E402
+from .batch_queue_conditional import *  # noqa: E402,F401,F403
 
 __all__ = ['Sup3rGan', 'Sup3rCondMom', 'Sup3rGanDC', 'SolarCC', 'Sup3rGanWithObs', 'MultiStepGan',
            'MultiStepSurfaceMetGan', 'LinearInterp', 'SurfaceSpatialMetModel', 'ForwardPass', 'ChunkPathOptions',
            'ChunkSlicer', 'DeviceBatchQueue', 'DeviceBatchHandler', 'DsetTuple',
-           '__version__']
+           *_cond.__all__, '__version__']

@@ -42,7 +42,7 @@ EXPORTS = [
     's3_time_mean', 's3_dft_axis',
     's3_specmap',
     's3_copy_channels', 's3_affine_channels', 's3_fill', 's3_copy_block',
-    's3_coarsen', 's3_gaussian_smooth', 's3_chunk_stats',
+    's3_coarsen', 's3_gaussian_smooth', 's3_condmom_target', 's3_chunk_stats',
     's3_st_interp', 's3_resize2d', 's3_surface_downscale',
     's3_chunk_epilogue', 's3_chunk_time_last', 's3_chunk_time_first',
     's3_step_handover', 's3_broadcast_axis',
@@ -215,6 +215,9 @@ def lib():
                              vp]),
         's3_gaussian_smooth': (i32, [vp, vp, i32, i32, i32, i32, i32, pf, i32,
                                      C.c_uint32, vp, vp]),
+        's3_condmom_target': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32,
+                                    i32, i32, C.POINTER(i32), i32, i32,
+                                    C.c_uint32, i32, i32, i32, vp, vp]),
         's3_st_interp': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp,
                                vp]),
         's3_resize2d': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp,
@@ -279,6 +282,7 @@ DGRAD_KERNELS = ('direct', 'mfma_frame', 'mfma_valid', 'mfma_chunked',
                  'fewch_frame', 's2', 'c2', 'gconv', 'fewpos')
 
 TC_METHODS = {'subsample': 0, 'average': 1, 'total': 2, 'max': 3, 'min': 4}
+CM_SUBFILTER, CM_LINEAR, CM_MOM1, CM_SQUARE = 1, 2, 4, 8
 
 
 def last_error(ctx):

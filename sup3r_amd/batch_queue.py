@@ -362,19 +362,25 @@ class DeviceBatchHandler(DeviceBatchQueue):
     builds its samplers from data containers; here ready samplers are handed
     in (duck-typed, see the module docstring) and ``means`` / ``stds`` are the
     per-feature dicts the model stores for ``norm_input`` / ``un_norm_output``
-    (``StatsCollection`` is part of the data layer)."""
+    (``StatsCollection`` is part of the data layer).
+
+    ``VAL_QUEUE`` is the class of the validation queue; a handler of another
+    queue class (batch_queue_conditional.py) names that class here and lists
+    it as a base behind this one, ``queue_kwargs`` then reach both queues."""
+
+    VAL_QUEUE = DeviceBatchQueue
 
     def __init__(self, train_samplers, val_samplers=None, batch_size=16,
                  n_batches=64, s_enhance=1, t_enhance=1, means=None, stds=None,
                  queue_cap=None, transform_kwargs=None, max_workers=1,
-                 mode='lazy', transform=None, seed=None):
+                 mode='lazy', transform=None, seed=None, **queue_kwargs):
         common = dict(batch_size=batch_size, n_batches=n_batches,
                       s_enhance=s_enhance, t_enhance=t_enhance,
                       queue_cap=queue_cap, transform_kwargs=transform_kwargs,
                       max_workers=max_workers, mode=mode, transform=transform,
-                      seed=seed)
+                      seed=seed, **queue_kwargs)
         super().__init__(samplers=train_samplers, **common)
-        self.val_data = DeviceBatchQueue(
+        self.val_data = self.VAL_QUEUE(
             samplers=val_samplers, thread_name='validation',
             **common) if val_samplers else []
         feats = self.features

@@ -211,6 +211,18 @@ class HipGanCompute:
             exo[name] = e
         return exo
 
+    def combine_loss_input(self, hr_true, hr_gen):
+        """_combine_loss_input (abstract.py:438-459): the generator's output
+        with the truth's trailing (exogenous) channels behind it, so that
+        both sides of the loss have the same channels."""
+        c_true, c_gen = hr_true.shape[-1], hr_gen.shape[-1]
+        if c_true <= c_gen:
+            return hr_gen
+        gen_full = self.dev.empty(tuple(hr_true.shape))
+        self._copy_channels(hr_gen, 0, gen_full, 0, c_gen)
+        self._copy_channels(hr_true, c_gen, gen_full, c_gen, c_true - c_gen)
+        return gen_full
+
     # -------------------------------------------------------------- forward
     def tf_generate(self, low_res, hi_res_exo=None, training=False):
         x = self.dev.to_device(low_res)
@@ -304,14 +316,7 @@ class HipGanCompute:
             gph = None
             hr_gen = dev.to_device(hi_res_gen)
         c_gen = hr_gen.shape[-1]
-        # _combine_loss_input (abstract.py:438-459)
-        if c_true > c_gen:
-            gen_full = dev.empty(tuple(hr_true.shape))
-            self._copy_channels(hr_gen, 0, gen_full, 0, c_gen)
-            self._copy_channels(hr_true, c_gen, gen_full, c_gen,
-                                c_true - c_gen)
-        else:
-            gen_full = hr_gen
+        gen_full = self.combine_loss_input(hr_true, hr_gen)
         if tuple(gen_full.shape) != tuple(hr_true.shape):
             raise RuntimeError(
                 'The tensor shapes of the synthetic output {} and true high '

@@ -444,6 +444,22 @@ class Sup3rGan:
             raise RuntimeError('generator failed on input of shape '
                                f'{tuple(np.shape(low_res))}') from e
 
+    def get_hr_exo_input(self, hi_res_true):
+        """abstract.py:415-436: the hi-res exogenous inputs of the generator,
+        taken from the trailing channels of the true hi-res batch — a dict
+        exo layer name -> device tensor (..., 1)."""
+        dev = self._compute.dev
+        return self._compute.exo_from_true(dev.to_device(hi_res_true),
+                                           list(self.hr_exo_features))
+
+    def _combine_loss_input(self, hi_res_true, hi_res_gen):
+        """abstract.py:438-459: ``hi_res_gen`` with the exogenous channels
+        of ``hi_res_true`` appended (a device tensor; ``hi_res_gen`` itself
+        when there are none)."""
+        dev = self._compute.dev
+        return self._compute.combine_loss_input(dev.to_device(hi_res_true),
+                                                dev.to_device(hi_res_gen))
+
     def discriminate(self, hi_res, norm_in=False):
         """base.py:237-281: numpy in, numpy logits out."""
         hi_res = np.asarray(numpy_if_tensor(hi_res))
