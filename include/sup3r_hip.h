@@ -611,6 +611,101 @@ int s3_condmom_target(s3_ctx* ctx, const float* hr, const float* lr, const float
                       unsigned flags, int s_pad, int t_lo, int t_hi, float* out,
                       float* mask);
 
+/* ---- bias correction of forward-pass chunks on the device ------------------
+ * replaces the host numpy / rex of ForwardPassStrategy.prep_chunk_data
+ * (sup3r/pipeline/strategy.py:502-517 -> bias_correct_features ->
+ * sup3r/bias/bias_transforms.py) for a batch of equal-shaped chunks that are
+ * ALREADY reflect-padded (forward_pass.py:66-72,122-186):
+ *   x, out  (n, s1, s2, t, c) fp32; out may be x.  n <= S3_BC_MAX_CHUNKS,
+ *           c <= S3_BC_MAX_CHANNELS.
+ *   channels_host[c]  one descriptor per channel (host); kind S3_BC_NONE
+ *           passes the channel through.  Table pointers are DEVICE pointers:
+ *           domain tables (S1, S2, n_t[, n_q]) resident for the whole low-res
+ *           domain; with S3_BC_PER_CHUNK per-chunk tables (n, s1, s2, n_t[,
+ *           n_q]) padded like the chunks themselves (smoothed factors,
+ *           bias_transforms.py:334-341,465-472); with S3_BC_GLOBAL one row
+ *           for every pixel (global_linear_bc, :224-248).
+ *   geom_host[n][6]   per chunk: o1, o2 = origin of the chunk's in-domain
+ *           window in the domain tables; lo1, lo2 = reflect padding in front
+ *           of it; e1, e2 = its un-padded extents.  Pixel (i, j) of the padded
+ *           chunk reads table row (o1 + reflect(i - lo1, e1), o2 + reflect(j -
+ *           lo2, e2)), reflect = the index map of np.pad(mode='reflect'): the
+ *           reference corrects the window and pads the result, which is the
+ *           same values.
+ *   month, window     device int32 (n, t): per time step of the padded chunk
+ *           the month (0 .. 11; S3_BC_MONTH) / the QDM time window
+ *           (argmin |doy - time_window_center|, bias_transforms.py:788-791),
+ *           mirrored along time by the host.  NULL if no channel needs it.
+ *   weights           device fp64 (n, n_t): S3_BC_WEIGHTS, the share of each
+ *           month in the chunk's time index; scalar = sum_m w_m table[i, j, m]
+ *           (accumulated in fp64, rounded once) stands for the mean over the
+ *           gathered months of temporal_avg=True (:442-448).
+ * S3_BC_LINEAR: out = x * scalar + adder, multiply and add rounded separately
+ *   (numpy's float32 arithmetic); S3_BC_SCALAR_RANGE / S3_BC_ADDER_RANGE clamp
+ *   the factors with np.minimum(f, hi) then np.maximum(f, lo) (:474-480).
+ * S3_BC_QDM (empirical distribution, linear sampling): with the rows oh, mh,
+ *   mf (n_q quantile values each) at (i, j, window) and levels q_k = k / (n_q
+ *   - 1): q = interp(x, mf, q_k), x_oh = interp(q, q_k, oh), x_mh = interp(q,
+ *   q_k, mh), interp = numpy.interp (clamped at both ends; on repeated knots
+ *   the segment is the last j with xp[j] <= x).  S3_BC_RELATIVE: x_mh = 0 ->
+ *   denom_zero (S3_BC_DENOM_ZERO), x_mh = max(x_mh, denom_min)
+ *   (S3_BC_DENOM_MIN), delta = x / x_mh, out = x_oh * delta; otherwise delta =
+ *   x - x_mh, out = x_oh + delta; S3_BC_DELTA_RANGE clamps delta (Cannon et
+ *   al. 2015, eqs. 3-6).  S3_BC_NO_TREND uses mh in place of mf.
+ *   S3_BC_PRESRAT (without S3_BC_NO_TREND): out = out < tau[i, j] ? 0 : out *
+ *   kfac[i, j, window] (:1115-1120).
+ * S3_BC_OUT_RANGE: np.maximum(out, out_lo) then np.minimum(out, out_hi), last
+ *   (:483-485, :813-815).
+ * mean_host / std_host (c doubles each, or NULL): the result is written
+ *   normalised, (out - mean) / std, with the arithmetic of
+ *   s3_chunk_time_first (fp32 when stats_fp32, fp64 rounded once otherwise),
+ *   every channel, corrected or not.
+ * nonfinite: device int32[c], ADDED to: the number of corrected values per
+ *   channel that are not finite (:816, NaN or inf) — with S3_BC_PRESRAT that
+ *   are NaN (:1128 tests isnan only); the RuntimeError of :816-823,
+ *   :1128-1135 is the caller's.
+ * S3_EINVAL: more chunks / channels than the limits, a window that leaves the
+ * padded chunk or the domain tables, a channel without the tables or index
+ * arrays its kind and flags need. */
+#define S3_BC_MAX_CHANNELS 16
+#define S3_BC_MAX_CHUNKS 32
+#define S3_BC_NONE 0
+#define S3_BC_LINEAR 1
+#define S3_BC_QDM 2
+#define S3_BC_MONTH 1u
+#define S3_BC_WEIGHTS 2u
+#define S3_BC_SCALAR_RANGE 4u
+#define S3_BC_ADDER_RANGE 8u
+#define S3_BC_OUT_RANGE 16u
+#define S3_BC_PER_CHUNK 32u
+#define S3_BC_RELATIVE 64u
+#define S3_BC_NO_TREND 128u
+#define S3_BC_DENOM_ZERO 256u
+#define S3_BC_DENOM_MIN 512u
+#define S3_BC_DELTA_RANGE 1024u
+#define S3_BC_PRESRAT 2048u
+#define S3_BC_GLOBAL 4096u
+typedef struct s3_bias_channel {
+  int32_t kind;              /* S3_BC_NONE / LINEAR / QDM */
+  uint32_t flags;
+  int32_t n_t;               /* last table axis: 1 or 12 months / QDM windows */
+  int32_t n_q;               /* quantiles per QDM row */
+  const float* scalar;       /* LINEAR (.., n_t) */
+  const float* adder;
+  const float* oh;           /* QDM (.., n_t, n_q): base_{base_dset}_params */
+  const float* mh;           /*     bias_{feature}_params */
+  const float* mf;           /*     bias_fut_{feature}_params */
+  const float* tau;          /* PRESRAT (..): {feature}_tau_fut */
+  const float* kfac;         /*     (.., n_t): {feature}_k_factor */
+  float scalar_lo, scalar_hi, adder_lo, adder_hi, out_lo, out_hi;
+  float delta_lo, delta_hi, denom_min, denom_zero;
+} s3_bias_channel;
+int s3_bias_correct(s3_ctx* ctx, const float* x, int n, int s1, int s2, int t, int c,
+                    const s3_bias_channel* channels_host, int S1, int S2,
+                    const int32_t* geom_host, const int32_t* month, const int32_t* window,
+                    const double* weights, const double* mean_host, const double* std_host,
+                    int stats_fp32, float* out, int32_t* nonfinite);
+
 /* ---- non-neural downscalers on the device ------------
  * replaces the host scipy / Pillow of the reference's LinearInterp and
  * SurfaceSpatialMetModel (sup3r/models/linear.py, sup3r/models/surface.py):

@@ -22,10 +22,14 @@ from .linear import LinearInterp  # noqa: E402,F401
 from .surface import SurfaceSpatialMetModel  # noqa: E402,F401
 from .batch_queue import (DeviceBatchHandler, DeviceBatchQueue,  # noqa: E402,F401
                           DsetTuple)
+from .bias import (BiasParams, DeviceBiasCorrection,  # noqa: E402,F401
+                   global_linear_bc, local_linear_bc, local_presrat_bc,
+                   local_qdm_bc, monthly_local_linear_bc)
 from . import batch_queue_conditional as _cond  # noqa: E402
 from .batch_queue_conditional import *  # noqa: E402,F401,F403
 
 __all__ = ['Sup3rGan', 'Sup3rCondMom', 'Sup3rGanDC', 'SolarCC', 'Sup3rGanWithObs', 'MultiStepGan',
            'MultiStepSurfaceMetGan', 'LinearInterp', 'SurfaceSpatialMetModel', 'ForwardPass', 'ChunkPathOptions',
-           'ChunkSlicer', 'DeviceBatchQueue', 'DeviceBatchHandler', 'DsetTuple',
+           'ChunkSlicer', 'BiasParams', 'DeviceBiasCorrection', 'global_linear_bc', 'local_linear_bc',
+           'monthly_local_linear_bc', 'local_qdm_bc', 'local_presrat_bc', 'DeviceBatchQueue', 'DeviceBatchHandler', 'DsetTuple',
            *_cond.__all__, '__version__']

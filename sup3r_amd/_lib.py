@@ -42,7 +42,7 @@ EXPORTS = [
     's3_time_mean', 's3_dft_axis',
     's3_specmap',
     's3_copy_channels', 's3_affine_channels', 's3_fill', 's3_copy_block',
-    's3_coarsen', 's3_gaussian_smooth', 's3_condmom_target', 's3_chunk_stats',
+    's3_coarsen', 's3_gaussian_smooth', 's3_condmom_target', 's3_bias_correct', 's3_chunk_stats',
     's3_st_interp', 's3_resize2d', 's3_surface_downscale',
     's3_chunk_epilogue', 's3_chunk_time_last', 's3_chunk_time_first',
     's3_step_handover', 's3_broadcast_axis',
@@ -67,6 +67,21 @@ class PlanOptions(C.Structure):
 
 class TensorDesc(C.Structure):
     _fields_ = [('dims', C.c_int64 * 5)]
+
+
+class BiasChannel(C.Structure):
+    """``s3_bias_channel``: the per-channel descriptor of s3_bias_correct"""
+    _fields_ = [
+        ('kind', C.c_int32), ('flags', C.c_uint32), ('n_t', C.c_int32),
+        ('n_q', C.c_int32), ('scalar', C.c_void_p), ('adder', C.c_void_p),
+        ('oh', C.c_void_p), ('mh', C.c_void_p), ('mf', C.c_void_p),
+        ('tau', C.c_void_p), ('kfac', C.c_void_p),
+        ('scalar_lo', C.c_float), ('scalar_hi', C.c_float),
+        ('adder_lo', C.c_float), ('adder_hi', C.c_float),
+        ('out_lo', C.c_float), ('out_hi', C.c_float),
+        ('delta_lo', C.c_float), ('delta_hi', C.c_float),
+        ('denom_min', C.c_float), ('denom_zero', C.c_float),
+    ]
 
 
 class OpDesc(C.Structure):
@@ -218,6 +233,11 @@ def lib():
         's3_condmom_target': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32,
                                     i32, i32, C.POINTER(i32), i32, i32,
                                     C.c_uint32, i32, i32, i32, vp, vp]),
+        's3_bias_correct': (i32, [vp, vp, i32, i32, i32, i32, i32,
+                                  C.POINTER(BiasChannel), i32, i32,
+                                  C.POINTER(i32), vp, vp, vp,
+                                  C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double), i32, vp, vp]),
         's3_st_interp': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp,
                                vp]),
         's3_resize2d': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp,
@@ -283,6 +303,12 @@ DGRAD_KERNELS = ('direct', 'mfma_frame', 'mfma_valid', 'mfma_chunked',
 
 TC_METHODS = {'subsample': 0, 'average': 1, 'total': 2, 'max': 3, 'min': 4}
 CM_SUBFILTER, CM_LINEAR, CM_MOM1, CM_SQUARE = 1, 2, 4, 8
+# s3_bias_correct: limits, channel kinds, flags (include/sup3r_hip.h)
+BC_MAX_CHANNELS, BC_MAX_CHUNKS = 16, 32
+BC_NONE, BC_LINEAR, BC_QDM = 0, 1, 2
+(BC_MONTH, BC_WEIGHTS, BC_SCALAR_RANGE, BC_ADDER_RANGE, BC_OUT_RANGE,
+ BC_PER_CHUNK, BC_RELATIVE, BC_NO_TREND, BC_DENOM_ZERO, BC_DENOM_MIN,
+ BC_DELTA_RANGE, BC_PRESRAT, BC_GLOBAL) = (1 << i for i in range(13))
 
 
 def last_error(ctx):

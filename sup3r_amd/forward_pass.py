@@ -926,7 +926,8 @@ class ForwardPass:
                    tuple((f, tuple(tuple(st['data'].shape)
                                    for st in e['steps']))
                          for f, e in sorted((chunk.exo_data or {}).items())),
-                   tuple((s_.start, s_.stop) for s_ in chunk.hr_crop_slice))
+                   tuple((s_.start, s_.stop) for s_ in chunk.hr_crop_slice),
+                   cls._bias_key(chunk))
             if group and (key != shape or len(group) >= batch):
                 pending.append(cls._launch_chunk_batch(
                     group, model, allowed_const, invert_uv, nn_fill, meta,
@@ -945,6 +946,7 @@ class ForwardPass:
     def _run_chunk_host(cls, chunk, model, allowed_const, invert_uv, nn_fill,
                         meta, output_workers, write):
         """forward_pass.py:640-672 through ``model.generate``"""
+        cls._bias_correct_host(chunk, model)
         output_data = cls.run_generator(
             data_chunk=chunk.input_data, hr_crop_slices=chunk.hr_crop_slice,
             s_enhance=model.s_enhance, t_enhance=model.t_enhance,
@@ -954,6 +956,45 @@ class ForwardPass:
             cls._write_chunk(chunk, model, output_data, invert_uv, nn_fill,
                              meta, output_workers)
         return chunk, failed, output_data
+
+    @staticmethod
+    def _bias_key(chunk):
+        rec = getattr(chunk, 'bias_correct', None)
+        return None if rec is None else (rec.method, id(rec.shared))
+
+    @staticmethod
+    def _bias_correct_host(chunk, model):
+        """a chunk that carries a ``bias_correct`` record and goes on through
+        host numpy (``model.generate``, a model's own ``norm_input``): its
+        input is corrected with the public transforms of ``sup3r_amd.bias`` —
+        the un-padded window, then the reflect padding again, the reference's
+        order (strategy.py:502-517, forward_pass.py:66-72)"""
+        if getattr(chunk, 'bias_correct', None) is None:
+            return
+        from .bias import correct_chunk_host
+        first = getattr(model, 'models', [model])[0]
+        n_own = np.asarray(chunk.input_data).shape[-1]
+        chunk.input_data = correct_chunk_host(
+            chunk, list(first.lr_features)[:n_own])
+        chunk.bias_correct = None
+
+    @staticmethod
+    def _device_bias(group, first, dev):
+        """the ``DeviceBiasCorrection`` of a group whose chunks carry a
+        ``bias_correct`` record (tables uploaded once per strategy and
+        device), and the chunks' windows"""
+        from .bias import ChunkWindow, DeviceBiasCorrection
+        rec = group[0].bias_correct
+        key = ('device', dev.index, tuple(first.lr_features))
+        bc = rec.shared.get(key)
+        if bc is None:
+            bc = rec.shared[key] = DeviceBiasCorrection(
+                rec.method, rec.kwargs, first.lr_features, dev=dev,
+                lat_lon=rec.lat_lon,
+                domain_shape=getattr(rec, 'domain_shape', None))
+        windows = [ChunkWindow(c.bias_correct.lr_pad_slice, c.pad_width,
+                               c.bias_correct.time_index) for c in group]
+        return bc, windows
 
     @classmethod
     def _write_chunk(cls, chunk, model, data, invert_uv, nn_fill, meta,
@@ -1021,10 +1062,21 @@ class ForwardPass:
         # (s3_chunk_time_first, numpy's arithmetic) unless the model brings
         # its own norm_input
         from .gan import Sup3rGan as _BaseGan
+        base_norm = getattr(type(first).norm_input, '__func__',
+                            type(first).norm_input) is _BaseGan.norm_input
         dev_norm = is_4d and options.device_norm_4d and \
-            not any(step_exo(e, 0) for e in exos) and \
-            getattr(type(first).norm_input, '__func__',
-                    type(first).norm_input) is _BaseGan.norm_input
+            not any(step_exo(e, 0) for e in exos) and base_norm
+        # chunks that carry a ``bias_correct`` record (raw input): corrected
+        # on the device — fused with the normalisation for a 5-D model, in
+        # place in front of s3_chunk_time_first for a 4-D one — unless the
+        # model normalises for itself or the batch is combined on the host
+        bias_dev = getattr(group[0], 'bias_correct', None) is not None
+        if bias_dev and not (base_norm and (dev_norm or not is_4d) and
+                             len(first.lr_features) <= _lib.BC_MAX_CHANNELS):
+            for chunk in group:
+                cls._bias_correct_host(chunk, model)
+            bias_dev = False
+        bias_counts = bias_bc = None
         for chunk, exo in zip(group, exos):
             # (one flat pass; the per-feature reduction over a (…, 2 .. 8)-wide
             # last axis — 0.7 ms per 75 x 75 x 48 chunk — only when it found one)
@@ -1036,6 +1088,12 @@ class ForwardPass:
                 raise RuntimeError(msg)
             if dev_norm:
                 xs.append(np.asarray(chunk.input_data, dtype=np.float32))
+                continue
+            if bias_dev:
+                # raw, with the 'input' exo channels: normalised by the kernel
+                xs.append(np.asarray(first._combine_fwp_input(
+                    np.asarray(chunk.input_data)[None],
+                    cls._batch_axis(step_exo(exo, 0))), dtype=np.float32))
                 continue
             if is_4d:
                 # (s1, s2, t, f) -> the t time steps as the batch of a 2-D
@@ -1174,11 +1232,13 @@ class ForwardPass:
             _lib.check(rc, dev.ctx, 's3_step_handover')
             return xn, nxt4
         try:
-            if dev_norm:
-                rawd = cls._upload_async(dev, raw, staged)
+            if dev_norm or bias_dev:
+                rawd = cls._upload_async(dev, raw if dev_norm else x, staged)
                 xd = dev.empty(x_shape)
                 mu = sd = None
                 f32 = 1
+                if bias_dev:
+                    bias_bc, windows = cls._device_bias(group, first, dev)
                 if first._means is not None:
                     mu, sd = first._stats_for(first.lr_features)
                     if len(mu) != x_shape[-1]:
@@ -1195,6 +1255,20 @@ class ForwardPass:
                     mu = np.ascontiguousarray(mu, dtype=np.float64)
                     sd = np.ascontiguousarray(sd, dtype=np.float64)
                 pd = C.POINTER(C.c_double)
+            if bias_dev and not dev_norm:
+                # 5-D: correction + normalisation in one pass (s3_bias_correct)
+                _, bias_counts = bias_bc.correct(
+                    rawd, windows, out=xd, mean=mu, std=sd, stats_fp32=f32,
+                    upload=lambda a: cls._upload_async(dev, a, staged,
+                                                       a.dtype),
+                    keep=staged)
+            elif dev_norm:
+                if bias_dev:
+                    _, bias_counts = bias_bc.correct(
+                        rawd, windows,
+                        upload=lambda a: cls._upload_async(dev, a, staged,
+                                                       a.dtype),
+                        keep=staged)
                 rc = L.s3_chunk_time_first(
                     dev.ctx, C.c_void_p(rawd.data_ptr()), n,
                     (C.c_int64 * 3)(raw.shape[1], raw.shape[2], raw.shape[3]),
@@ -1370,6 +1444,10 @@ class ForwardPass:
             deliver()
             ev.synchronize()
             staged.clear()
+            if bias_counts is not None:
+                # (the batch has run: the reference's RuntimeError for QDM /
+                # PresRat results that are not finite)
+                bias_bc.check(bias_counts)
             st = stats_h.numpy().reshape(n, 64, n_out, 3)
             mn, mx = st[..., 0].min(1), st[..., 1].max(1)
             nn = st[..., 2].sum(1)
@@ -1461,7 +1539,7 @@ class ForwardPass:
     _upload_streams = {}
 
     @classmethod
-    def _upload_async(cls, dev, arr, keep):
+    def _upload_async(cls, dev, arr, keep, dtype=np.float32):
         """host array -> device tensor without blocking the host OR the compute
         stream: a pageable ``.to(device)`` on the compute stream returns only
         when the copy has run, i.e. after every kernel enqueued before it — the
@@ -1474,8 +1552,9 @@ class ForwardPass:
         idle; now it crosses PCIe under batch k's kernels and the compute
         stream only waits for its event)."""
         import torch
-        arr = np.ascontiguousarray(arr, dtype=np.float32)
-        stage = torch.empty(arr.shape, dtype=torch.float32, pin_memory=True)
+        arr = np.ascontiguousarray(arr, dtype=dtype)
+        stage = torch.empty(arr.shape, dtype=getattr(torch, arr.dtype.name),
+                            pin_memory=True)
         stage.numpy()[...] = arr
         keep.append(stage)
         with cls._lane_lock:

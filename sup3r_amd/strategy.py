@@ -11,8 +11,11 @@ is the in-memory counterpart of ``ForwardPassStrategy`` for the attributes
 the executor reads (``init_chunk`` strategy.py:520-581, ``node_chunks``
 :363-372, ``chunk_finished``, ``model_kwargs`` / ``model_class`` /
 ``allowed_const`` / ``invert_uv`` / ``nn_fill`` / ``output_workers``): file
-IO, bias correction and exo rasterisation stay in sup3r (out of
-scope), here the lo-res domain and the exo fields are arrays.
+IO and exo rasterisation stay in sup3r (out of scope), here the
+lo-res domain and the exo fields are arrays.  Bias correction
+(``bias_correct_method`` / ``bias_correct_kwargs``, strategy.py:502-517) is
+not applied here: ``init_chunk`` attaches a ``bias_correct`` record to the raw
+chunk and the executor corrects the batch on the device (``sup3r_amd.bias``).
 """
 import copy
 import os
@@ -126,6 +129,9 @@ class ForwardPassChunk:
     out_file: str
     pad_width: tuple
     index: int
+    #: ``bias.BiasCorrectRecord`` of a chunk whose ``input_data`` is still raw
+    #: (``ArrayStrategy(bias_correct_method=...)``); None: nothing to correct
+    bias_correct: object = None
 
     def __post_init__(self):
         self.shape = self.input_data.shape
@@ -140,15 +146,46 @@ class ArrayStrategy:
     resolution (``ExoData``, preprocessing/data_handlers/exo.py:54-273); 3-D
     ``(s1, s2, 1)`` fields are constant in time.  ``max_nodes``: number of
     nodes (= ranks, one per GPU) the chunk list is split over with
-    ``np.array_split`` like strategy.py:363-372."""
+    ``np.array_split`` like strategy.py:363-372.
+
+    ``bias_correct_method`` / ``bias_correct_kwargs`` (strategy.py:139-151):
+    the name of a transform of ``sup3r_amd.bias`` and feature -> its keyword
+    arguments; ``input_time_index``: the low-res ``DatetimeIndex`` of the
+    domain's time axis, which the monthly / QDM / PresRat methods need;
+    ``input_lat_lon``: the low-res ``(s1, s2, 2)`` coordinates the factor
+    tables are matched to when they carry ``latitude`` / ``longitude``.  The
+    chunks then carry a ``bias_correct`` record and raw ``input_data``."""
 
     def __init__(self, domain, model_kwargs, fwp_chunk_shape, spatial_pad=1,
                  temporal_pad=1, model_class='Sup3rGan', exo_data=None,
                  out_pattern=None, allowed_const=False, invert_uv=False,
                  nn_fill=True, output_workers=None, max_nodes=1,
                  lat_lon=None, time_index=None, meta=None, s_enhance=None,
-                 t_enhance=None, model=None):
+                 t_enhance=None, model=None, bias_correct_method=None,
+                 bias_correct_kwargs=None, input_time_index=None,
+                 input_lat_lon=None):
         from .forward_pass import get_model
+        self.bias_correct_method = bias_correct_method
+        self.bias_correct_kwargs = bias_correct_kwargs or {}
+        self.input_time_index = input_time_index
+        self.input_lat_lon = input_lat_lon
+        self._bias_shared = {}
+        if bias_correct_method is not None:
+            from .bias import METHODS, TIME_METHODS
+            if bias_correct_method not in METHODS:
+                raise KeyError(
+                    f'unknown bias_correct_method "{bias_correct_method}"; '
+                    f'have {METHODS}')
+            if bias_correct_method in TIME_METHODS and \
+                    input_time_index is None:
+                raise ValueError(
+                    f'bias_correct_method "{bias_correct_method}" needs '
+                    'input_time_index, the low-res DatetimeIndex')
+            if input_time_index is not None and \
+                    len(input_time_index) != domain.shape[2]:
+                raise ValueError(
+                    f'input_time_index has {len(input_time_index)} steps, '
+                    f'the domain {domain.shape[2]}')
         self.domain = domain
         self.model_kwargs = model_kwargs
         self.model_class = model_class
@@ -255,7 +292,18 @@ class ArrayStrategy:
             n1, n2 = sl.hr_shape[:2]
             self._gids = np.arange(n1 * n2).reshape(n1, n2)
         gids = self._gids[hr[0], hr[1]]
+        record = None
+        if self.bias_correct_method is not None and self.bias_correct_kwargs:
+            from .bias import BiasCorrectRecord
+            ti = self.input_time_index
+            record = BiasCorrectRecord(
+                self.bias_correct_method, self.bias_correct_kwargs,
+                c['lr_pad_slice'],
+                None if ti is None else ti[c['lr_pad_slice'][2]],
+                lat_lon=self.input_lat_lon, shared=self._bias_shared,
+                domain_shape=tuple(self.domain.shape[:2]))
         return ForwardPassChunk(
+            bias_correct=record,
             input_data=data, exo_data=self._exo_chunk(c['lr_pad_slice']),
             lr_pad_slice=c['lr_pad_slice'], hr_crop_slice=c['hr_crop'],
             hr_lat_lon=lat_lon, hr_times=times, gids=gids,
