@@ -102,7 +102,29 @@ enum { S3_STAT_PERSIST_DGRAD = 0, /* trunk data gradients on the persistent kern
        S3_STAT_DGRAD_C2_SLIDE = 3, /* first-layer data gradients on the sliding kernel */
        S3_STAT_BUCKETS = 4,       /* bucket collectives issued under backward passes */
        S3_STAT_ALLREDUCES = 5,    /* whole-buffer / scalar all-reduces issued        */
-       S3_STAT_COUNT = 6 };
+       /* support passes of the training step (kernels_misc.hip), one per kernel launched */
+       S3_STAT_BIAS_STAGE1 = 6,     /* bias gradient: one channel per lane (bias_grad_stage1)   */
+       S3_STAT_BIAS_STAGE1_V4 = 7,  /* bias gradient: four channels per lane (bias_grad_stage1_v4) */
+       S3_STAT_BIAS_COLS = 8,       /* bias gradient: > 256 channels, one serial walk per channel */
+       S3_STAT_BIAS_COLS_SPLIT = 9, /* bias gradient: > 256 channels, rows split over blockIdx.y */
+       S3_STAT_BIAS_PARTIAL = 10,   /* stage 2 over riding channel sums, launched at once       */
+       S3_STAT_BIAS_PARTIAL_RIDE = 11, /* ... deferred, run inside a weight-gradient reduction  */
+       S3_STAT_BIAS_PARTIAL_FLUSH = 12, /* ... deferred, launched on its own when nothing took it */
+       S3_STAT_EPI_GENERIC = 13,    /* mask pass: one element per lane (conv_epilogue_bwd_kernel) */
+       S3_STAT_EPI_C4 = 14,         /* mask pass: four channels per lane, no store permutation  */
+       S3_STAT_EPI_D2S4 = 15,       /* mask pass: four channels per lane, depth-to-space walk   */
+       S3_STAT_EPI_C4_BSUM = 16,    /* ... of EPI_C4, those with riding channel sums            */
+       S3_STAT_EPI_D2S4_BSUM = 17,  /* ... of EPI_D2S4, those with riding channel sums          */
+       S3_STAT_FOLD_GATHER = 18,    /* adjoint of a gather op, one element per lane             */
+       S3_STAT_FOLD_PAD4 = 19,      /* fold of an fp32 frame, four channels per lane            */
+       S3_STAT_FOLD_PAD4_FR16 = 20, /* fold of a bf16 frame, four channels per lane             */
+       S3_STAT_FOLD16X8 = 21,       /* fold of a bf16 frame, eight channels per lane            */
+       S3_STAT_FOLD_PLAIN = 22,     /* frame folds (the three above) with no mask               */
+       S3_STAT_FOLD_MASKED = 23,    /* ... with the producer's activation adjoint fused         */
+       S3_STAT_FOLD_ADD = 24,       /* ... added to an earlier gradient contribution            */
+       S3_STAT_AXPY = 25,           /* skip accumulation, one element per lane                  */
+       S3_STAT_AXPY4 = 26,          /* skip accumulation, four elements per lane                */
+       S3_STAT_COUNT = 27 };
 int64_t s3_ctx_stat(const s3_ctx* ctx, int which);
 
 /* ---- parameter store ---------------------------------------------------

@@ -265,7 +265,15 @@ def lib():
 
 
 STATS = {'persist_dgrad': 0, 'gconv_splitk': 1, 'bucket_elems': 2,
-         'dgrad_c2_slide': 3, 'buckets': 4, 'allreduces': 5}
+         'dgrad_c2_slide': 3, 'buckets': 4, 'allreduces': 5,
+         # support passes of the training step, one per kernel launched
+         'bias_stage1': 6, 'bias_stage1_v4': 7, 'bias_cols': 8,
+         'bias_cols_split': 9, 'bias_partial': 10, 'bias_partial_ride': 11,
+         'bias_partial_flush': 12, 'epi_generic': 13, 'epi_c4': 14,
+         'epi_d2s4': 15, 'epi_c4_bsum': 16, 'epi_d2s4_bsum': 17,
+         'fold_gather': 18, 'fold_pad4': 19, 'fold_pad4_fr16': 20,
+         'fold16x8': 21, 'fold_plain': 22, 'fold_masked': 23, 'fold_add': 24,
+         'axpy': 25, 'axpy4': 26}
 
 
 def option_names():

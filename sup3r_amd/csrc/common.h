@@ -144,7 +144,7 @@ struct s3_ctx {
   float* scratch = nullptr;  // small device scratch (reductions)
   size_t scratch_bytes = 0;
   int num_cu = 256;
-  int64_t stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // S3_STAT_* launch counters
+  int64_t stat[S3_STAT_COUNT] = {};   // S3_STAT_* launch counters
   S3Options opt;                     // defaults of the plans created from this context
   hipStream_t comm_stream = nullptr; // bucketed gradient all-reduce under the backward pass
   hipEvent_t comm_ev[2] = {nullptr, nullptr};   // [0] compute -> comm, [1] comm -> compute

@@ -587,6 +587,7 @@ static int launch_wgrad_bf16_reduce(s3_ctx* ctx, const float* partial, int n_par
   const int extra = j.partial ? j.c : 0;
   hipLaunchKernelGGL(wgrad_bf16_partial_reduce, dim3(wblocks + extra), dim3(256), 0, ctx->stream, partial,
                      n_part, wsize, dw, accumulate, wblocks, j.partial, j.nblk, j.c, j.db, j.accumulate);
+  if (extra) ++ctx->stat[S3_STAT_BIAS_PARTIAL_RIDE];
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }

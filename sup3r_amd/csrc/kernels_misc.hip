@@ -1218,6 +1218,7 @@ int launch_gather_bwd_masked(s3_ctx* ctx, const GatherGeom& g, const float* dout
     if (out_bf16) { if (y_bf16) S3_FOLD8(2, true); else S3_FOLD8(1, true); }
     else { if (y_bf16) S3_FOLD8(2, false); else S3_FOLD8(1, false); }
 #undef S3_FOLD8
+    ++ctx->stat[S3_STAT_FOLD16X8]; ++ctx->stat[S3_STAT_FOLD_MASKED];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
@@ -1229,6 +1230,7 @@ int launch_gather_bwd_masked(s3_ctx* ctx, const GatherGeom& g, const float* dout
     if (out_bf16) { if (y_bf16) S3_FOLD16(2, true); else S3_FOLD16(1, true); }
     else { if (y_bf16) S3_FOLD16(2, false); else S3_FOLD16(1, false); }
 #undef S3_FOLD16
+    ++ctx->stat[S3_STAT_FOLD_PAD4_FR16]; ++ctx->stat[S3_STAT_FOLD_MASKED];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
@@ -1240,6 +1242,7 @@ int launch_gather_bwd_masked(s3_ctx* ctx, const GatherGeom& g, const float* dout
     else
       hipLaunchKernelGGL((gather_bwd_pad4_kernel<1, true>), grid16, dim3(kBlock), 0, ctx->stream, dout, din, g, mask_y,
                          slope, bsum);
+    ++ctx->stat[S3_STAT_FOLD_PAD4]; ++ctx->stat[S3_STAT_FOLD_MASKED];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
@@ -1248,6 +1251,7 @@ int launch_gather_bwd_masked(s3_ctx* ctx, const GatherGeom& g, const float* dout
     hipLaunchKernelGGL(gather_bwd_pad4_kernel<2>, grid, dim3(kBlock), 0, ctx->stream, dout, din, g, mask_y, slope, bsum);
   else
     hipLaunchKernelGGL(gather_bwd_pad4_kernel<1>, grid, dim3(kBlock), 0, ctx->stream, dout, din, g, mask_y, slope, bsum);
+  ++ctx->stat[S3_STAT_FOLD_PAD4]; ++ctx->stat[S3_STAT_FOLD_MASKED];
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }
@@ -1267,6 +1271,7 @@ int launch_bias_grad_from_partial(s3_ctx* ctx, const float* partial, int nblk, i
     return S3_OK;
   }
   hipLaunchKernelGGL(bias_grad_stage2, dim3(c), dim3(256), 0, ctx->stream, partial, nblk, c, db, accumulate);
+  ++ctx->stat[S3_STAT_BIAS_PARTIAL];
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }
@@ -1276,6 +1281,7 @@ int s3_flush_pending_bias(s3_ctx* ctx) {
   const s3_ctx::PendingBias j = ctx->pend_bias;
   ctx->pend_bias.partial = nullptr;
   hipLaunchKernelGGL(bias_grad_stage2, dim3(j.c), dim3(256), 0, ctx->stream, j.partial, j.nblk, j.c, j.db, j.accumulate);
+  ++ctx->stat[S3_STAT_BIAS_PARTIAL_FLUSH];
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }
@@ -1295,6 +1301,7 @@ int launch_gather_bwd_add(s3_ctx* ctx, const GatherGeom& g, const float* dout, f
       hipLaunchKernelGGL((fold16x8_kernel<3, false, false>), gridf, dim3(kBlock), 0, ctx->stream,
                          (const unsigned short*)dout, din, g, (const void*)add, 0.f, bsum,
                          (unsigned short*)nullptr);
+    ++ctx->stat[S3_STAT_FOLD16X8]; ++ctx->stat[S3_STAT_FOLD_ADD];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
@@ -1306,17 +1313,20 @@ int launch_gather_bwd_add(s3_ctx* ctx, const GatherGeom& g, const float* dout, f
     else
       hipLaunchKernelGGL((gather_bwd_pad4_kernel<3, false, false, true>), dim3(grid_for(n / 4, ctx->num_cu)),
                          dim3(kBlock), 0, ctx->stream, dout, din, g, (const void*)add, 0.f, bsum);
+    ++ctx->stat[S3_STAT_FOLD_PAD4_FR16]; ++ctx->stat[S3_STAT_FOLD_ADD];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
   if (side16) {
     hipLaunchKernelGGL((gather_bwd_pad4_kernel<3, false, true>), dim3(grid_for(n / 4, ctx->num_cu)), dim3(kBlock), 0,
                        ctx->stream, dout, din, g, (const void*)add, 0.f, bsum, (unsigned short*)side16);
+    ++ctx->stat[S3_STAT_FOLD_PAD4]; ++ctx->stat[S3_STAT_FOLD_ADD];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
   hipLaunchKernelGGL(gather_bwd_pad4_kernel<3>, dim3(grid_for(n / 4, ctx->num_cu)), dim3(kBlock), 0, ctx->stream,
                      dout, din, g, (const void*)add, 0.f, bsum);
+  ++ctx->stat[S3_STAT_FOLD_PAD4]; ++ctx->stat[S3_STAT_FOLD_ADD];
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }
@@ -1334,6 +1344,7 @@ int launch_gather_bwd(s3_ctx* ctx, const GatherGeom& g, const float* dout,
       hipLaunchKernelGGL((fold16x8_kernel<0, false, false>), gridf, dim3(kBlock), 0, ctx->stream,
                          (const unsigned short*)dout, din, g, (const void*)nullptr, 0.f, (float*)nullptr,
                          (unsigned short*)nullptr);
+    ++ctx->stat[S3_STAT_FOLD16X8]; ++ctx->stat[S3_STAT_FOLD_PLAIN];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
@@ -1346,6 +1357,7 @@ int launch_gather_bwd(s3_ctx* ctx, const GatherGeom& g, const float* dout,
     else
       hipLaunchKernelGGL((gather_bwd_pad4_kernel<0, false, false, true>), dim3(grid_for(n / 4, ctx->num_cu)),
                          dim3(kBlock), 0, ctx->stream, dout, din, g, (const void*)nullptr, 0.f, (float*)nullptr);
+    ++ctx->stat[S3_STAT_FOLD_PAD4_FR16]; ++ctx->stat[S3_STAT_FOLD_PLAIN];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
@@ -1354,16 +1366,19 @@ int launch_gather_bwd(s3_ctx* ctx, const GatherGeom& g, const float* dout,
     hipLaunchKernelGGL((gather_bwd_pad4_kernel<0, false, true>), dim3(grid_for(n / 4, ctx->num_cu)), dim3(kBlock), 0,
                        ctx->stream, dout, din, g, (const void*)nullptr, 0.f, (float*)nullptr,
                        (unsigned short*)side16);
+    ++ctx->stat[S3_STAT_FOLD_PAD4]; ++ctx->stat[S3_STAT_FOLD_PLAIN];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
   if (g.kind == S3_OP_PAD && g.Ci == g.Co && (g.Ci & 3) == 0) {
     hipLaunchKernelGGL(gather_bwd_pad4_kernel<0>, dim3(grid_for(n / 4, ctx->num_cu)), dim3(kBlock), 0,
                        ctx->stream, dout, din, g, (const void*)nullptr, 0.f, (float*)nullptr);
+    ++ctx->stat[S3_STAT_FOLD_PAD4]; ++ctx->stat[S3_STAT_FOLD_PLAIN];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
   hipLaunchKernelGGL(gather_bwd_kernel, dim3(grid_for(n, ctx->num_cu)), dim3(kBlock), 0, ctx->stream, dout, din, g);
+  ++ctx->stat[S3_STAT_FOLD_GATHER];
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }
@@ -1429,6 +1444,8 @@ int launch_conv_epilogue_bwd(s3_ctx* ctx, const ConvGeom& g, const float* y,
     else
       hipLaunchKernelGGL(conv_epilogue_bwd4_kernel<false>, grid, dim3(kBlock), 0, ctx->stream, (const void*)y,
                          (const float4*)dy, (float4*)dpre, n4, slope, (unsigned short*)d16, bsum, g.Cout >> 2);
+    ++ctx->stat[S3_STAT_EPI_C4];
+    if (bsum) ++ctx->stat[S3_STAT_EPI_C4_BSUM];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
@@ -1450,6 +1467,8 @@ int launch_conv_epilogue_bwd(s3_ctx* ctx, const ConvGeom& g, const float* y,
     else
       hipLaunchKernelGGL(conv_epilogue_bwd_d2s4_kernel<false>, grid, dim3(kBlock), 0, ctx->stream, (const void*)y,
                          (const float4*)dy, (float4*)dpre, g, slope);
+    ++ctx->stat[S3_STAT_EPI_D2S4];
+    if (y_bf16 && d16 && bsum) ++ctx->stat[S3_STAT_EPI_D2S4_BSUM];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
@@ -1457,6 +1476,7 @@ int launch_conv_epilogue_bwd(s3_ctx* ctx, const ConvGeom& g, const float* y,
     hipLaunchKernelGGL(conv_epilogue_bwd_kernel<true>, dim3(grid_for(n, ctx->num_cu)), dim3(kBlock), 0, ctx->stream, y, dy, dpre, g);
   else
     hipLaunchKernelGGL(conv_epilogue_bwd_kernel<false>, dim3(grid_for(n, ctx->num_cu)), dim3(kBlock), 0, ctx->stream, y, dy, dpre, g);
+  ++ctx->stat[S3_STAT_EPI_GENERIC];
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }
@@ -1480,10 +1500,12 @@ int launch_axpy(s3_ctx* ctx, const float* x, float* y, int64_t n) {
   if ((n & 3) == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
     hipLaunchKernelGGL(axpy4_kernel, dim3(grid_for(n / 4, ctx->num_cu)), dim3(kBlock), 0, ctx->stream,
                        (const float4*)x, (float4*)y, n / 4);
+    ++ctx->stat[S3_STAT_AXPY4];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
   hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n, ctx->num_cu)), dim3(kBlock), 0, ctx->stream, x, y, n);
+  ++ctx->stat[S3_STAT_AXPY];
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }
@@ -1505,11 +1527,13 @@ int launch_bias_grad(s3_ctx* ctx, const float* dy, int64_t n_pos, int c,
       int rc = ensure_scratch(ctx, (size_t)ns * c * sizeof(float));
       if (rc) return rc;
       hipLaunchKernelGGL(bias_grad_cols_split, dim3(cb, ns), dim3(256), 0, ctx->stream, dy, n_pos, c, ctx->scratch);
+      ++ctx->stat[S3_STAT_BIAS_COLS_SPLIT];
       hipLaunchKernelGGL(bias_grad_stage2, dim3(c), dim3(256), 0, ctx->stream, ctx->scratch, ns, c, db, accumulate);
       S3_HIP(ctx, hipGetLastError());
       return S3_OK;
     }
     hipLaunchKernelGGL(bias_grad_cols, dim3((c + 255) / 256), dim3(256), 0, ctx->stream, dy, n_pos, c, db, accumulate);
+    ++ctx->stat[S3_STAT_BIAS_COLS];
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
@@ -1528,8 +1552,11 @@ int launch_bias_grad(s3_ctx* ctx, const float* dy, int64_t n_pos, int c,
     if (want4 < nblk) nblk = (int)(want4 < 1 ? 1 : want4);
     hipLaunchKernelGGL(bias_grad_stage1_v4, dim3(nblk), dim3(block), block * sizeof(float4), ctx->stream,
                        (const float4*)dy, n_pos, c4, ctx->scratch);
-  } else
-  hipLaunchKernelGGL(bias_grad_stage1, dim3(nblk), dim3(block), block * sizeof(float), ctx->stream, dy, n_pos, c, ctx->scratch);
+    ++ctx->stat[S3_STAT_BIAS_STAGE1_V4];
+  } else {
+    hipLaunchKernelGGL(bias_grad_stage1, dim3(nblk), dim3(block), block * sizeof(float), ctx->stream, dy, n_pos, c, ctx->scratch);
+    ++ctx->stat[S3_STAT_BIAS_STAGE1];
+  }
   hipLaunchKernelGGL(bias_grad_stage2, dim3(c), dim3(256), 0, ctx->stream, ctx->scratch, nblk, c, db, accumulate);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
