@@ -19,15 +19,21 @@ MI355X design points:
     reflect at domain edges) so one plan serves the whole domain.
 """
 import collections
+import ctypes as C
 import json
 import logging
 import os
+from warnings import warn
 
 import numpy as np
 
+from . import _lib
 from .strategy import (ArrayStrategy, ChunkSlicer,  # noqa: F401
                        ForwardPassChunk, chunk_slices)
+from .utilities import ExoData
 
+# (torch is imported where a device is at hand: the CPU suite imports this
+# module)
 logger = logging.getLogger(__name__)
 
 _MODELS = {}
@@ -205,6 +211,148 @@ def _read_ahead(chunks, depth):
             yield c
     finally:
         stop.set()
+
+
+# -- leaf steps both executors (``iter_chunks``, ``run_batched``) take --------
+_PF, _PD = C.POINTER(C.c_float), C.POINTER(C.c_double)
+_I64X3 = C.c_int64 * 3
+
+#: what ``iter_chunks`` was called with, handed down as one value
+_RunSettings = collections.namedtuple('_RunSettings', [
+    'allowed_const', 'invert_uv', 'nn_fill', 'meta', 'output_workers',
+    'return_data', 'write', 'lane', 'options'])
+
+
+def _vp(t):
+    """a device tensor's address as the C-ABI takes it"""
+    return C.c_void_p(t.data_ptr())
+
+
+def _fptr(a, ptr=_PF):
+    """a host array (or None) as the C-ABI takes it"""
+    return None if a is None else a.ctypes.data_as(ptr)
+
+
+def _is_base_method(m, name):
+    """``m`` takes ``name`` from ``Sup3rGan`` itself (the device paths
+    re-implement the base class's arithmetic, not an override's)"""
+    from .gan import Sup3rGan
+    f = getattr(type(m), name, None)
+    return getattr(f, '__func__', f) is getattr(Sup3rGan, name)
+
+
+def _unnorm_affine(model):
+    """``(scale, shift)`` of the model's un-normalisation ``y * std + mean``
+    per output feature, float32 — ``(None, None)`` without statistics"""
+    if model.means is None:
+        return None, None
+    mu, sd = model._stats_for(model.hr_out_features)
+    return (np.ascontiguousarray(sd, dtype=np.float32),
+            np.ascontiguousarray(mu, dtype=np.float32))
+
+
+def _nonzero_std(sd):
+    """abstract.py:197-238: a zero standard deviation divides by 1"""
+    if (sd == 0).any():
+        warn('a feature has zero standard deviation; dividing by 1')
+        sd = np.where(sd == 0, 1, sd)
+    return sd
+
+
+def _affine_channels(dev, y, scale, shift):
+    """``y * scale + shift`` per channel in place (s3_affine_channels)"""
+    if scale is None:
+        return
+    n_out = int(y.shape[-1])
+    rc = _lib.lib().s3_affine_channels(
+        dev.ctx, _vp(y), _vp(y), n_out, y.numel() // n_out, _fptr(scale),
+        _fptr(shift))
+    _lib.check(rc, dev.ctx, 's3_affine_channels')
+
+
+def _crop_blocks(dev, y, cr, yc):
+    """the halo crop chunk by chunk: ``y[k][cr] -> yc[k]`` of a full-size
+    ``(n, y1, y2, y3, c)`` batch, ``cr`` = ``_crop_bounds`` (s3_copy_block)"""
+    L = _lib.lib()
+    y2, y3, c = (int(v) for v in y.shape[2:])
+    c1, c2, c3 = (b - a for a, b in cr)
+    for k in range(int(yc.shape[0])):
+        src = y[k].data_ptr() + 4 * c * (
+            (cr[0][0] * y2 + cr[1][0]) * y3 + cr[2][0])
+        rc = L.s3_copy_block(
+            dev.ctx, C.c_void_p(src), _vp(yc[k]), c1, c2, c3 * c,
+            y2 * y3 * c, y3 * c, c2 * c3 * c, c3 * c)
+        _lib.check(rc, dev.ctx, 's3_copy_block')
+
+
+def _chunk_stats(dev, yc):
+    """min / max / NaN count per chunk and channel of the cropped batch, in
+    64 partial slots per chunk: ``(n, 64, c, 3)`` on the device
+    (s3_chunk_stats)"""
+    n, c = int(yc.shape[0]), int(yc.shape[-1])
+    stats_d = dev.empty((n, 64, c, 3))
+    rc = _lib.lib().s3_chunk_stats(dev.ctx, _vp(yc), n,
+                                   yc.numel() // (n * c), c, _vp(stats_d))
+    _lib.check(rc, dev.ctx, 's3_chunk_stats')
+    return stats_d
+
+
+def _stats_to_host(stats_d, copy_stream, also=None, also_reads=()):
+    """the statistics' download into pinned memory on the copy stream, behind
+    what the compute stream holds now.  ``also()`` enqueues the caller's
+    payload copy on that stream in front of it (it reads the tensors
+    ``also_reads``).  Returns ``(stats_h, ready, ev)``: ``ready`` = the
+    compute stream got here, ``ev`` = the copies are done."""
+    import torch
+    stats_h = torch.empty(tuple(stats_d.shape), dtype=torch.float32,
+                          pin_memory=True)
+    ready = torch.cuda.Event()
+    ready.record()
+    with torch.cuda.stream(copy_stream):
+        copy_stream.wait_event(ready)
+        if also is not None:
+            also()
+        stats_h.copy_(stats_d, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(copy_stream)
+    for t in also_reads:
+        t.record_stream(copy_stream)
+    stats_d.record_stream(copy_stream)
+    return stats_h, ready, ev
+
+
+def _verdicts(stats, allowed_const, log=False):
+    """``_output_check`` from the ``(n, 64, c, 3)`` statistics of
+    ``_chunk_stats``: per chunk, True = failed (a NaN, or a channel that is
+    one constant not listed in ``allowed_const``).  ``log``: say why."""
+    skip, allowed = ForwardPass._const_ok(allowed_const)
+    if skip:
+        return [False] * len(stats)
+    mn, mx = stats[..., 0].min(1), stats[..., 1].max(1)
+    nn = stats[..., 2].sum(1)
+    fails = []
+    for k in range(len(stats)):
+        msg = None
+        if nn[k].any():
+            msg = 'Forward pass output contains NaN values!'
+        else:
+            for i in range(mn.shape[1]):
+                if mn[k, i] == mx[k, i] and mn[k, i] not in allowed:
+                    msg = f'All values are the same for feature channel {i}!'
+                    break
+        if log and msg is not None:
+            logger.error(msg)
+        fails.append(msg is not None)
+    return fails
+
+
+def _fused_epilogue_ok(n_out, c3, lo3, y3):
+    """s3_chunk_epilogue walks float4s: the channel count divides 1024 (at
+    most 16) and the rows — the crop's extent ``c3``, its start ``lo3`` and
+    the full extent ``y3`` along the last axis, times the channels — are
+    16-byte aligned"""
+    return 1024 % n_out == 0 and n_out <= 16 and not any(
+        (v * n_out) % 4 for v in (c3, lo3, y3))
 
 
 class ForwardPass:
@@ -525,12 +673,9 @@ class ForwardPass:
 
         Supports single-step 5-D models without exogenous inputs; anything
         else falls back to :meth:`run`."""
-        import ctypes as C
         from concurrent.futures import ThreadPoolExecutor
 
         import torch
-
-        from . import _lib
         model, sl = self.model, self.slicer
         gen = getattr(model, '_gen', None)
         # (models that override generate — SolarCC's temporal padding — or
@@ -558,11 +703,7 @@ class ForwardPass:
             dom_d = self.upload_domain(domain).tensor
         n_in = int(dom_d.shape[-1])
         n_out = len(model.hr_out_features)
-        if model.means is not None:
-            mu, sd = model._stats_for(model.hr_out_features)
-            scale = np.ascontiguousarray(sd, dtype=np.float32)
-            shift = np.ascontiguousarray(mu, dtype=np.float32)
-        pf = C.POINTER(C.c_float)
+        scale, shift = _unnorm_affine(model)
 
         # chunks grouped by padded input shape (edge chunks are ragged)
         groups = {}
@@ -596,21 +737,31 @@ class ForwardPass:
             elif out is not None:
                 out[hr_sl] = data
 
+        def to_windows(yc, cids):
+            # one pitched copy per chunk into its window of ``out``, on the
+            # copy stream
+            c1, c2 = int(yc.shape[1]), int(yc.shape[2])
+            row = int(yc.shape[3]) * int(yc.shape[4])
+            st0, st1 = out.strides[0] // 4, out.strides[1] // 4
+            for k, idx in enumerate(cids):
+                hs = sl.chunks[idx]['hr_slice']
+                dst = out.ctypes.data + 4 * (
+                    hs[0].start * st0 + hs[1].start * st1
+                    + hs[2].start * n_out)
+                rc = L.s3_d2h_window(
+                    dev.ctx, _vp(yc[k]), C.c_void_p(dst), c1, c2, row, st0,
+                    st1, C.c_void_p(copy_stream.cuda_stream))
+                _lib.check(rc, dev.ctx, 's3_d2h_window')
+
         def drain(keep):
             while len(pending) > keep:
                 ev, buf, cids, stats = pending.pop(0)
                 ev.synchronize()
-                if direct:
-                    buf = None        # (device block kept alive until here)
-                st = stats.numpy().reshape(len(cids), 64, n_out, 3)
-                mn, mx = st[..., 0].min(1), st[..., 1].max(1)
-                nn = st[..., 2].sum(1)
-                skip, allowed = self._const_ok(self.allowed_const)
-                for k, idx in enumerate(cids):
-                    const = [v for v, w in zip(mn[k], mx[k]) if v == w]
-                    bad = not skip and (
-                        nn[k].any() or any(v not in allowed for v in const))
-                    if self.output_check and bad:
+                fails = _verdicts(
+                    stats.numpy().reshape(len(cids), 64, n_out, 3),
+                    self.allowed_const)
+                for idx, failed in zip(cids, fails):
+                    if self.output_check and failed:
                         raise MemoryError('Forward pass output check failed '
                                           f'on chunk {idx}')
                 if not direct:
@@ -649,92 +800,38 @@ class ForwardPass:
                             'the low res / high res shapes of {} -> {}'.format(
                                 sl.s_enhance, sl.t_enhance, tuple(x.shape),
                                 tuple(y.shape)))
-                    if model.means is not None:
-                        rc = L.s3_affine_channels(
-                            dev.ctx, C.c_void_p(y.data_ptr()),
-                            C.c_void_p(y.data_ptr()), n_out,
-                            y.numel() // n_out, scale.ctypes.data_as(pf),
-                            shift.ctypes.data_as(pf))
-                        _lib.check(rc, dev.ctx, 's3_affine_channels')
+                    _affine_channels(dev, y, scale, shift)
                     # halo crop (the same for every chunk of a shape group)
-                    crop = sl.chunks[cids[0]]['hr_crop']
-                    y1, y2, y3 = (int(v) for v in y.shape[1:4])
-                    cr = [(s_.start or 0, y_ if s_.stop is None else s_.stop)
-                          for s_, y_ in zip(crop, (y1, y2, y3))]
-                    cr = [(a, b if b >= 0 else y_ + b)
-                          for (a, b), y_ in zip(cr, (y1, y2, y3))]
-                    c1, c2, c3 = (b - a for a, b in cr)
-                    yc = dev.empty((len(cids), c1, c2, c3, n_out))
-                    for k in range(len(cids)):
-                        src = y[k].data_ptr() + 4 * n_out * (
-                            (cr[0][0] * y2 + cr[1][0]) * y3 + cr[2][0])
-                        rc = L.s3_copy_block(
-                            dev.ctx, C.c_void_p(src),
-                            C.c_void_p(yc[k].data_ptr()), c1, c2, c3 * n_out,
-                            y2 * y3 * n_out, y3 * n_out, c2 * c3 * n_out,
-                            c3 * n_out)
-                        _lib.check(rc, dev.ctx, 's3_copy_block')
-                    stats_d = dev.empty((len(cids), 64, n_out, 3))
-                    rc = L.s3_chunk_stats(
-                        dev.ctx, C.c_void_p(yc.data_ptr()), len(cids),
-                        yc.numel() // (len(cids) * n_out), n_out,
-                        C.c_void_p(stats_d.data_ptr()))
-                    _lib.check(rc, dev.ctx, 's3_chunk_stats')
-                    key = tuple(yc.shape)
+                    cr = self._crop_bounds(sl.chunks[cids[0]]['hr_crop'],
+                                           tuple(y.shape[1:4]))
+                    yc = dev.empty((len(cids),) + tuple(
+                        b - a for a, b in cr) + (n_out,))
+                    _crop_blocks(dev, y, cr, yc)
+                    stats_d = _chunk_stats(dev, yc)
                     if direct:
                         drain(2)
-                        stats_h = torch.empty(tuple(stats_d.shape),
-                                              dtype=torch.float32,
-                                              pin_memory=True)
-                        ready = torch.cuda.Event()
-                        ready.record()
-                        with torch.cuda.stream(copy_stream):
-                            copy_stream.wait_event(ready)
-                            cs1, cs2 = int(yc.shape[1]), int(yc.shape[2])
-                            row = int(yc.shape[3]) * int(yc.shape[4])
-                            st0 = out.strides[0] // 4
-                            st1 = out.strides[1] // 4
-                            for k, idx in enumerate(cids):
-                                hs = sl.chunks[idx]['hr_slice']
-                                dst = out.ctypes.data + 4 * (
-                                    hs[0].start * st0 + hs[1].start * st1
-                                    + hs[2].start * n_out)
-                                rc = L.s3_d2h_window(
-                                    dev.ctx, C.c_void_p(yc[k].data_ptr()),
-                                    C.c_void_p(dst), cs1, cs2, row, st0, st1,
-                                    C.c_void_p(copy_stream.cuda_stream))
-                                _lib.check(rc, dev.ctx, 's3_d2h_window')
-                            stats_h.copy_(stats_d, non_blocking=True)
-                            ev = torch.cuda.Event()
-                            ev.record(copy_stream)
-                        yc.record_stream(copy_stream)
-                        stats_d.record_stream(copy_stream)
-                        pending.append((ev, yc, cids, stats_h))
-                        done += len(cids)
-                        continue
-                    if key not in pinned:
-                        pinned[key] = [torch.empty(key, dtype=torch.float32,
-                                                   pin_memory=True)
-                                       for _ in range(n_ring)]
-                        toggle[key] = 0
-                    # at most n_ring - 1 batches between D2H and placement
-                    drain(n_ring - 2)
-                    buf = pinned[key][toggle[key]]
-                    toggle[key] = (toggle[key] + 1) % n_ring
-                    for f in busy.pop(id(buf), []):
-                        f.result()        # (re-raises a writer's exception)
-                    stats_h = torch.empty(tuple(stats_d.shape),
-                                          dtype=torch.float32, pin_memory=True)
-                    ready = torch.cuda.Event()
-                    ready.record()
-                    with torch.cuda.stream(copy_stream):
-                        copy_stream.wait_event(ready)
-                        buf.copy_(yc, non_blocking=True)
-                        stats_h.copy_(stats_d, non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record(copy_stream)
-                    yc.record_stream(copy_stream)
-                    stats_d.record_stream(copy_stream)
+                        # (the device block stays alive until it is drained)
+                        buf, payload = yc, lambda: to_windows(yc, cids)
+                    else:
+                        key = tuple(yc.shape)
+                        if key not in pinned:
+                            pinned[key] = [
+                                torch.empty(key, dtype=torch.float32,
+                                            pin_memory=True)
+                                for _ in range(n_ring)]
+                            toggle[key] = 0
+                        # at most n_ring - 1 batches between D2H and placement
+                        drain(n_ring - 2)
+                        buf = pinned[key][toggle[key]]
+                        toggle[key] = (toggle[key] + 1) % n_ring
+                        for f in busy.pop(id(buf), []):
+                            f.result()    # (re-raises a writer's exception)
+
+                        def payload():
+                            buf.copy_(yc, non_blocking=True)
+                    # the payload crosses first, then the statistics
+                    stats_h, _, ev = _stats_to_host(
+                        stats_d, copy_stream, also=payload, also_reads=(yc,))
                     pending.append((ev, buf, cids, stats_h))
                     done += len(cids)
             drain(0)
@@ -790,17 +887,12 @@ class ForwardPass:
         statistics and 'input' exo fields, at most 16 channels at a
         hand-over, no 'output' exo: the hand-overs stay on the device
         (s3_step_handover); anything else through ``MultiStepGan.generate``"""
-        from .gan import Sup3rGan as _BaseGan
         steps = list(model.models)
         options = _opts(options)
         if not options.device_chains or not steps:
             return False
-
-        def base(m, name):
-            f = getattr(type(m), name, None)
-            return getattr(f, '__func__', f) is getattr(_BaseGan, name)
         seen_5d = False
-        for i, m in enumerate(steps):
+        for m in steps:
             if getattr(m, '_gen', None) is None or \
                     not getattr(m, 'supports_device_chunks', False) or \
                     hasattr(m, 'models'):
@@ -808,10 +900,9 @@ class ForwardPass:
             # (hand_over re-implements the base class's input combination on
             # the device: a step that overrides any of it goes through
             # MultiStepGan.generate)
-            if not all(base(m, name) for name in (
+            if not all(_is_base_method(m, name) for name in (
                     'norm_input', 'un_norm_output', 'generate',
-                    '_combine_fwp_input')
-                    if hasattr(_BaseGan, name)):
+                    '_combine_fwp_input')):
                 return False
             if getattr(m, 'is_5d', False):
                 seen_5d = True
@@ -828,8 +919,6 @@ class ForwardPass:
                         mu, sd = m._stats_for(feats)
                         if mu.dtype != np.float32 or sd.dtype != np.float32:
                             return False
-                elif i > 0 and steps[i - 1]._means is not None:
-                    pass
         for entry in (chunk.exo_data or {}).values():
             for st in entry['steps']:
                 if st['combine_type'].lower() == 'output':
@@ -882,45 +971,43 @@ class ForwardPass:
         out copies.  ``options``: a ``ChunkPathOptions`` (or a dict of its
         fields to change)."""
         options = _opts(options)
-        pending = collections.deque()
         # the delivery rings belong to THIS generator: two interleaved
         # ``iter_chunks`` runs (threads, two models with one output shape)
         # get different lanes, consecutive runs reuse lane 0's pinned buffers
         lane = cls._take_lane()
+        run = _RunSettings(allowed_const, invert_uv, nn_fill, meta,
+                           output_workers, return_data, write, lane, options)
         if options.input_prefetch and not isinstance(chunks, (list, tuple)):
             chunks = _read_ahead(chunks, options.input_prefetch)
         try:
-            yield from cls._iter_chunks_lane(
-                chunks, model, allowed_const, batch, invert_uv, nn_fill, meta,
-                output_workers, return_data, write, pending, lane, options)
+            yield from cls._iter_chunks_lane(chunks, model, batch, run)
         finally:
             cls._lanes.discard(lane)
 
     @classmethod
-    def _iter_chunks_lane(cls, chunks, model, allowed_const, batch, invert_uv,
-                          nn_fill, meta, output_workers, return_data, write,
-                          pending, lane, options):
+    def _iter_chunks_lane(cls, chunks, model, batch, run):
+        pending = collections.deque()
+
+        def launch(group):
+            pending.append(_ChunkBatch(group, model, run))
+
         def flush(keep):
             # the newest batch is on the device's queue: the one before it may
             # start crossing PCIe (its forward is the one running or done)
             if len(pending) > 1:
                 pending[-2].deliver()
             while len(pending) > keep:
-                yield from pending.popleft()()
+                yield from pending.popleft().finish()
 
         group, shape = [], None
         for chunk in chunks:
-            if not cls._device_path(model, chunk, options):
+            if not cls._device_path(model, chunk, run.options):
                 yield from flush(0)
                 if group:
-                    pending.append(cls._launch_chunk_batch(
-                        group, model, allowed_const, invert_uv, nn_fill, meta,
-                        output_workers, return_data, write, lane, options))
+                    launch(group)
                     group, shape = [], None
                     yield from flush(0)
-                yield cls._run_chunk_host(chunk, model, allowed_const,
-                                          invert_uv, nn_fill, meta,
-                                          output_workers, write)
+                yield cls._run_chunk_host(chunk, model, run)
                 continue
             key = (tuple(chunk.input_data.shape),
                    tuple((f, tuple(tuple(st['data'].shape)
@@ -929,32 +1016,27 @@ class ForwardPass:
                    tuple((s_.start, s_.stop) for s_ in chunk.hr_crop_slice),
                    cls._bias_key(chunk))
             if group and (key != shape or len(group) >= batch):
-                pending.append(cls._launch_chunk_batch(
-                    group, model, allowed_const, invert_uv, nn_fill, meta,
-                    output_workers, return_data, write, lane, options))
+                launch(group)
                 group = []
                 yield from flush(2)
             group.append(chunk)
             shape = key
         if group:
-            pending.append(cls._launch_chunk_batch(
-                group, model, allowed_const, invert_uv, nn_fill, meta,
-                output_workers, return_data, write, lane, options))
+            launch(group)
         yield from flush(0)
 
     @classmethod
-    def _run_chunk_host(cls, chunk, model, allowed_const, invert_uv, nn_fill,
-                        meta, output_workers, write):
+    def _run_chunk_host(cls, chunk, model, run):
         """forward_pass.py:640-672 through ``model.generate``"""
         cls._bias_correct_host(chunk, model)
         output_data = cls.run_generator(
             data_chunk=chunk.input_data, hr_crop_slices=chunk.hr_crop_slice,
             s_enhance=model.s_enhance, t_enhance=model.t_enhance,
             exo_data=chunk.exo_data, model=model)
-        failed = cls._output_check(output_data, allowed_const=allowed_const)
-        if write and chunk.out_file is not None and not failed:
-            cls._write_chunk(chunk, model, output_data, invert_uv, nn_fill,
-                             meta, output_workers)
+        failed = cls._output_check(output_data,
+                                   allowed_const=run.allowed_const)
+        if run.write and chunk.out_file is not None and not failed:
+            cls._write_chunk(chunk, model, output_data, run)
         return chunk, failed, output_data
 
     @staticmethod
@@ -997,8 +1079,7 @@ class ForwardPass:
         return bc, windows
 
     @classmethod
-    def _write_chunk(cls, chunk, model, data, invert_uv, nn_fill, meta,
-                     output_workers):
+    def _write_chunk(cls, chunk, model, data, run):
         """the output epilogue on the device (writers/base.py:304-345), then
         the registered writer for the file type"""
         from .output_transform import DeviceOutputTransform
@@ -1007,8 +1088,8 @@ class ForwardPass:
         tr = DeviceOutputTransform(model._gen.dev if getattr(
             model, '_gen', None) is not None else None)
         x, features = tr.transform_output(
-            data, features, chunk.hr_lat_lon, invert_uv=invert_uv,
-            nn_fill=nn_fill)
+            data, features, chunk.hr_lat_lon, invert_uv=run.invert_uv,
+            nn_fill=run.nn_fill)
         output_type = get_source_type(chunk.out_file)
         handler = cls.OUTPUT_HANDLER_CLASS.get(output_type)
         if handler is None:
@@ -1021,481 +1102,8 @@ class ForwardPass:
         handler._write_output(
             data=x.cpu().numpy(), features=features,
             lat_lon=chunk.hr_lat_lon, times=chunk.hr_times,
-            out_file=chunk.out_file, meta_data=meta, invert_uv=False,
-            nn_fill=False, max_workers=output_workers, gids=chunk.gids)
-
-    @classmethod
-    def _launch_chunk_batch(cls, group, model, allowed_const, invert_uv,
-                            nn_fill, meta, output_workers, return_data,
-                            write, lane=0, options=None):
-        """Enqueue one batch of equal-shaped chunks; returns the closure that
-        waits for it and yields its ``(chunk, failed, output_data)``."""
-        import ctypes as C
-
-        import torch
-
-        from . import _lib
-        from .utilities import ExoData
-        # a MultiStepGan chain runs step by step on the device; a single
-        # model is a chain of one
-        options = _opts(options)
-        chain = hasattr(model, 'models')
-        steps = list(model.models) if chain else [model]
-        first, last = steps[0], steps[-1]
-        gen = first._gen
-        dev, L = gen.dev, _lib.lib()
-        n = len(group)
-        is_4d = not getattr(first, 'is_5d', False)
-        xs, exos = [], []
-
-        def step_exo(exo, i):
-            """the exo entries model step ``i`` consumes (exo.py:108-130)"""
-            if exo is None or not chain:
-                return exo
-            return exo.get_model_step_exo(i)
-        for chunk in group:
-            exo = chunk.exo_data
-            if exo is not None and not isinstance(exo, ExoData):
-                exo = ExoData(exo)
-            exos.append(exo)
-        # 4-D models: transpose + normalisation on the device
-        # (s3_chunk_time_first, numpy's arithmetic) unless the model brings
-        # its own norm_input
-        from .gan import Sup3rGan as _BaseGan
-        base_norm = getattr(type(first).norm_input, '__func__',
-                            type(first).norm_input) is _BaseGan.norm_input
-        dev_norm = is_4d and options.device_norm_4d and \
-            not any(step_exo(e, 0) for e in exos) and base_norm
-        # chunks that carry a ``bias_correct`` record (raw input): corrected
-        # on the device — fused with the normalisation for a 5-D model, in
-        # place in front of s3_chunk_time_first for a 4-D one — unless the
-        # model normalises for itself or the batch is combined on the host
-        bias_dev = getattr(group[0], 'bias_correct', None) is not None
-        if bias_dev and not (base_norm and (dev_norm or not is_4d) and
-                             len(first.lr_features) <= _lib.BC_MAX_CHANNELS):
-            for chunk in group:
-                cls._bias_correct_host(chunk, model)
-            bias_dev = False
-        bias_counts = bias_bc = None
-        for chunk, exo in zip(group, exos):
-            # (one flat pass; the per-feature reduction over a (…, 2 .. 8)-wide
-            # last axis — 0.7 ms per 75 x 75 x 48 chunk — only when it found one)
-            if np.isnan(chunk.input_data).any():
-                mask = np.isnan(chunk.input_data).any(axis=(0, 1, 2))
-                feats = np.array(first.lr_features[:len(mask)])[mask]
-                msg = f'Input data for {feats} contains NaN values!'
-                logger.error(msg)
-                raise RuntimeError(msg)
-            if dev_norm:
-                xs.append(np.asarray(chunk.input_data, dtype=np.float32))
-                continue
-            if bias_dev:
-                # raw, with the 'input' exo channels: normalised by the kernel
-                xs.append(np.asarray(first._combine_fwp_input(
-                    np.asarray(chunk.input_data)[None],
-                    cls._batch_axis(step_exo(exo, 0))), dtype=np.float32))
-                continue
-            if is_4d:
-                # (s1, s2, t, f) -> the t time steps as the batch of a 2-D
-                # model (``_reshape_data_chunk``, forward_pass.py:274-337)
-                # (contiguous: the normalisation below walks a transposed
-                # view four times slower)
-                x = first._combine_fwp_input(np.ascontiguousarray(np.transpose(
-                    np.asarray(chunk.input_data), (2, 0, 1, 3))),
-                    cls._batch_axis(step_exo(exo, 0), time_first=True))
-            else:
-                x = first._combine_fwp_input(
-                    np.asarray(chunk.input_data)[None],
-                    cls._batch_axis(step_exo(exo, 0)))
-            xs.append(np.asarray(first.norm_input(x), dtype=np.float32))
-        if dev_norm:
-            raw = np.stack(xs, axis=0)                  # (n, s1, s2, t, f)
-            x_shape = (n * raw.shape[3], raw.shape[1], raw.shape[2],
-                       raw.shape[4])
-            x = None
-        else:
-            x = np.concatenate(xs, axis=0) if n > 1 else xs[0]
-            x_shape = tuple(x.shape)
-        n_t = x_shape[0] // n          # 4-D: time steps per chunk
-        lr_t = n_t if is_4d else x_shape[3]
-        staged = []               # pinned upload buffers, alive until finish()
-        pf = C.POINTER(C.c_float)
-        i64x3 = C.c_int64 * 3
-
-        def layer_exo_for(m, ph, i, rank4, nt):
-            """the 'layer' exo fields step ``i``'s generator consumes
-            mid-network, normalised, stacked over the batch, uploaded"""
-            out = {}
-            for name in ph.input_names:
-                if name == 'x':
-                    continue
-                fields = []
-                for exo in exos:
-                    e = step_exo(exo, i)
-                    assert e is not None and name in e, \
-                        f'the generator needs exogenous feature "{name}"'
-                    fields.append(np.asarray(
-                        e.get_combine_type_data(name, 'layer')))
-                out[name] = cls._exo_to_device(
-                    dev, fields, rank4, staged,
-                    lambda a, m=m, name=name: m._reshape_norm_exo(
-                        tuple(a.shape), a, name))
-                # (the plan of a 2-D model carries a time axis of one)
-                want = tuple(int(v) for v in ph.in_shapes[name])
-                if tuple(v for v in out[name].shape if v != 1) == \
-                        tuple(v for v in want if v != 1):
-                    out[name] = out[name].reshape(want)
-                if tuple(out[name].shape) != want:
-                    raise RuntimeError(
-                        f'exogenous "{name}" of shape '
-                        f'{tuple(out[name].shape)} cannot be laid over '
-                        f'hi-res {want}')
-            return out
-
-        def hand_over(i, y, rank4, nt):
-            """step i's normalised output -> step i + 1's normalised input
-            (multi_step.py:233-259) without leaving the device"""
-            m, nxt = steps[i], steps[i + 1]
-            ysh = tuple(int(v) for v in y.shape)
-            nxt4 = not getattr(nxt, 'is_5d', False)
-            if rank4 and not nxt4:
-                # (n t, H, W, C) -> n samples (H, W, t, C)
-                # (_transpose_model_input, multi_step.py:107-146)
-                yt = dev.empty((n, ysh[1], ysh[2], nt, ysh[3]))
-                rc = L.s3_chunk_time_last(
-                    dev.ctx, C.c_void_p(y.data_ptr()), n,
-                    i64x3(nt, ysh[1], ysh[2]), i64x3(0, 0, 0),
-                    i64x3(ysh[1], ysh[2], nt), ysh[3], None, None,
-                    C.c_void_p(yt.data_ptr()))
-                _lib.check(rc, dev.ctx, 's3_chunk_time_last')
-                y, ysh = yt, tuple(int(v) for v in yt.shape)
-            produced = list(m.hr_out_features)
-            if len(produced) != ysh[-1]:
-                raise RuntimeError(
-                    f'step {i} produced {ysh[-1]} channels for '
-                    f'{len(produced)} output features')
-            nxt_exo = [step_exo(e, i + 1) for e in exos]
-            wanted = [f for f in nxt.lr_features
-                      if f not in (nxt_exo[0] or {})]
-            missing = [f for f in wanted if f not in produced]
-            if missing:
-                raise ValueError(
-                    f'step {i + 1} needs {missing}, step {i} only produces '
-                    f'{produced}')
-            extra = len(nxt.lr_features) - len(wanted)
-            names = list(nxt.lr_features[-extra:]) if extra > 0 else []
-            exo_t = None
-            if names:
-                fields = []
-                for e in nxt_exo:
-                    absent = [f for f in names if f not in (e or {})]
-                    assert not absent, (f'exogenous_data lacks {absent} '
-                                        '(combine_type "input")')
-                    cols = [np.asarray(e.get_combine_type_data(f, 'input'))
-                            for f in names]
-                    fields.append(cols[0] if len(cols) == 1 else
-                                  np.concatenate(cols, axis=-1))
-                exo_t = cls._exo_to_device(dev, fields, nxt4, staged,
-                                           lambda a: a)
-                if tuple(exo_t.shape[:-1]) != ysh[:-1]:
-                    raise RuntimeError(
-                        f'"input" exo of step {i + 1} has shape '
-                        f'{tuple(exo_t.shape)}, the data {ysh}')
-            sc = sh_ = mu = sd = None
-            if m._means is not None:
-                mu0, sd0 = m._stats_for(m.hr_out_features)
-                sc = np.ascontiguousarray(sd0, dtype=np.float32)
-                sh_ = np.ascontiguousarray(mu0, dtype=np.float32)
-            if nxt._means is not None:
-                mu1, sd1 = nxt._stats_for(nxt.lr_features)
-                if (sd1 == 0).any():
-                    from warnings import warn
-                    warn('a feature has zero standard deviation; dividing '
-                         'by 1')
-                    sd1 = np.where(sd1 == 0, 1, sd1)
-                mu = np.ascontiguousarray(mu1, dtype=np.float32)
-                sd = np.ascontiguousarray(sd1, dtype=np.float32)
-            cmap = (C.c_int32 * len(wanted))(
-                *[produced.index(f) for f in wanted])
-            xn = dev.empty(ysh[:-1] + (len(wanted) + len(names),))
-            n_pos = int(np.prod(ysh[:-1], dtype=np.int64))
-            rc = L.s3_step_handover(
-                dev.ctx, C.c_void_p(y.data_ptr()), n_pos, ysh[-1], cmap,
-                len(wanted),
-                sc.ctypes.data_as(pf) if sc is not None else None,
-                sh_.ctypes.data_as(pf) if sh_ is not None else None,
-                C.c_void_p(exo_t.data_ptr()) if exo_t is not None else None,
-                len(names),
-                mu.ctypes.data_as(pf) if mu is not None else None,
-                sd.ctypes.data_as(pf) if sd is not None else None,
-                C.c_void_p(xn.data_ptr()))
-            _lib.check(rc, dev.ctx, 's3_step_handover')
-            return xn, nxt4
-        try:
-            if dev_norm or bias_dev:
-                rawd = cls._upload_async(dev, raw if dev_norm else x, staged)
-                xd = dev.empty(x_shape)
-                mu = sd = None
-                f32 = 1
-                if bias_dev:
-                    bias_bc, windows = cls._device_bias(group, first, dev)
-                if first._means is not None:
-                    mu, sd = first._stats_for(first.lr_features)
-                    if len(mu) != x_shape[-1]:
-                        raise RuntimeError(
-                            f'{len(mu)} normalisation statistics for '
-                            f'{x_shape[-1]} input features')
-                    if (sd == 0).any():
-                        from warnings import warn
-                        warn('a feature has zero standard deviation; '
-                             'dividing by 1')
-                        sd = np.where(sd == 0, 1, sd)
-                    f32 = int(mu.dtype == np.float32 and
-                              sd.dtype == np.float32)
-                    mu = np.ascontiguousarray(mu, dtype=np.float64)
-                    sd = np.ascontiguousarray(sd, dtype=np.float64)
-                pd = C.POINTER(C.c_double)
-            if bias_dev and not dev_norm:
-                # 5-D: correction + normalisation in one pass (s3_bias_correct)
-                _, bias_counts = bias_bc.correct(
-                    rawd, windows, out=xd, mean=mu, std=sd, stats_fp32=f32,
-                    upload=lambda a: cls._upload_async(dev, a, staged,
-                                                       a.dtype),
-                    keep=staged)
-            elif dev_norm:
-                if bias_dev:
-                    _, bias_counts = bias_bc.correct(
-                        rawd, windows,
-                        upload=lambda a: cls._upload_async(dev, a, staged,
-                                                       a.dtype),
-                        keep=staged)
-                rc = L.s3_chunk_time_first(
-                    dev.ctx, C.c_void_p(rawd.data_ptr()), n,
-                    (C.c_int64 * 3)(raw.shape[1], raw.shape[2], raw.shape[3]),
-                    x_shape[-1],
-                    mu.ctypes.data_as(pd) if mu is not None else None,
-                    sd.ctypes.data_as(pd) if sd is not None else None, f32,
-                    C.c_void_p(xd.data_ptr()))
-                _lib.check(rc, dev.ctx, 's3_chunk_time_first')
-            else:
-                xd = cls._upload_async(dev, x, staged)
-            # every step but the last: plan forward + hand-over on the device
-            in_shape = x_shape
-            for i in range(len(steps) - 1):
-                ph_i = steps[i]._gen.plan(x_shape, training=False)
-                y_i = ph_i.forward(xd, layer_exo_for(steps[i], ph_i, i, is_4d,
-                                                     n_t))
-                xd, is_4d = hand_over(i, y_i, is_4d, n_t)
-                del y_i
-                x_shape = tuple(int(v) for v in xd.shape)
-            ph = last._gen.plan(x_shape, training=False)
-            layer_exo = layer_exo_for(last, ph, len(steps) - 1, is_4d, n_t)
-            # the enhancement checks of the reference (forward_pass.py:
-            # _run_generator) on the plan's output shape
-            yshape = tuple(int(v) for v in ph.out_shape)
-            if model.s_enhance * in_shape[1] != yshape[1]:
-                msg = ('The stated spatial enhancement of {}x did not match '
-                       'the low res / high res shapes of {} -> {}'.format(
-                           model.s_enhance, in_shape, yshape))
-                logger.error(msg)
-                raise _EnhancementMismatch(msg)
-            if model.t_enhance * lr_t != (n_t if is_4d else yshape[3]):
-                msg = ('The stated temporal enhancement of {}x did not match '
-                       'the low res / high res shapes of {} -> {}'.format(
-                           model.t_enhance, in_shape, yshape))
-                logger.error(msg)
-                raise _EnhancementMismatch(msg)
-            n_out = yshape[-1]
-            scale = shift = None
-            if last.means is not None:
-                mu, sd = last._stats_for(last.hr_out_features)
-                scale = np.ascontiguousarray(sd, dtype=np.float32)
-                shift = np.ascontiguousarray(mu, dtype=np.float32)
-            # (4-D: the chunk's hi-res extents are (H, W, time steps))
-            y1, y2, y3 = (yshape[1], yshape[2], n_t) if is_4d else yshape[1:4]
-            cr = cls._crop_bounds(group[0].hr_crop_slice, (y1, y2, y3))
-            c1, c2, c3 = (b - a for a, b in cr)
-            yc = dev.empty((n, c1, c2, c3, n_out))
-            stats_d = dev.empty((n, 64, n_out, 3))
-            # halo crop + un-normalisation inside the tail conv (the window
-            # forward: no full-size output, halo positions of the last conv
-            # never computed) where the plan ends in the MFMA tail ...
-            windowed = options.window_forward and ph.supports_window and \
-                not is_4d
-            if windowed:
-                ph.forward_window(
-                    xd, layer_exo, yc, [cr[0][0], cr[1][0], cr[2][0]],
-                    [c1, c2, c3], cls._affine_tensor(dev, scale, shift))
-                y = None
-            else:
-                y = ph.forward(xd, layer_exo)
-        except (AssertionError, _EnhancementMismatch):
-            raise
-        except Exception as e:
-            msg = 'Forward pass failed on chunk with shape {}.'.format(
-                x_shape)
-            logger.exception(msg)
-            raise RuntimeError(msg) from e
-        # ... else un-normalisation, halo crop and the output check's
-        # statistics in one pass over the cropped window (s3_chunk_epilogue)
-        # where the rows are 16-byte aligned, the three separate kernels
-        # otherwise — same bits in every case
-        fused = 1024 % n_out == 0 and n_out <= 16 and not any(
-            (v * n_out) % 4 for v in (c3, cr[2][0], y3))
-        if is_4d:
-            # transpose to the chunk's (s1, s2, t) order + halo crop +
-            # un-normalisation in one pass, then the output check's statistics
-            i64x3 = C.c_int64 * 3
-            rc = L.s3_chunk_time_last(
-                dev.ctx, C.c_void_p(y.data_ptr()), n, i64x3(n_t, y1, y2),
-                i64x3(cr[0][0], cr[1][0], cr[2][0]), i64x3(c1, c2, c3), n_out,
-                scale.ctypes.data_as(pf) if scale is not None else None,
-                shift.ctypes.data_as(pf) if shift is not None else None,
-                C.c_void_p(yc.data_ptr()))
-            _lib.check(rc, dev.ctx, 's3_chunk_time_last')
-            rc = L.s3_chunk_stats(dev.ctx, C.c_void_p(yc.data_ptr()), n,
-                                  yc.numel() // (n * n_out), n_out,
-                                  C.c_void_p(stats_d.data_ptr()))
-            _lib.check(rc, dev.ctx, 's3_chunk_stats')
-        elif windowed:
-            rc = L.s3_chunk_stats(dev.ctx, C.c_void_p(yc.data_ptr()), n,
-                                  yc.numel() // (n * n_out), n_out,
-                                  C.c_void_p(stats_d.data_ptr()))
-            _lib.check(rc, dev.ctx, 's3_chunk_stats')
-        elif fused:
-            i64x3 = C.c_int64 * 3
-            rc = L.s3_chunk_epilogue(
-                dev.ctx, C.c_void_p(y.data_ptr()), n, i64x3(y1, y2, y3),
-                i64x3(cr[0][0], cr[1][0], cr[2][0]), i64x3(c1, c2, c3), n_out,
-                scale.ctypes.data_as(pf) if scale is not None else None,
-                shift.ctypes.data_as(pf) if shift is not None else None,
-                C.c_void_p(yc.data_ptr()), C.c_void_p(stats_d.data_ptr()))
-            _lib.check(rc, dev.ctx, 's3_chunk_epilogue')
-        else:
-            if scale is not None:
-                rc = L.s3_affine_channels(
-                    dev.ctx, C.c_void_p(y.data_ptr()),
-                    C.c_void_p(y.data_ptr()), n_out, y.numel() // n_out,
-                    scale.ctypes.data_as(pf), shift.ctypes.data_as(pf))
-                _lib.check(rc, dev.ctx, 's3_affine_channels')
-            for k in range(n):
-                src = y[k].data_ptr() + 4 * n_out * (
-                    (cr[0][0] * y2 + cr[1][0]) * y3 + cr[2][0])
-                rc = L.s3_copy_block(
-                    dev.ctx, C.c_void_p(src), C.c_void_p(yc[k].data_ptr()),
-                    c1, c2, c3 * n_out, y2 * y3 * n_out, y3 * n_out,
-                    c2 * c3 * n_out, c3 * n_out)
-                _lib.check(rc, dev.ctx, 's3_copy_block')
-            rc = L.s3_chunk_stats(dev.ctx, C.c_void_p(yc.data_ptr()), n,
-                                  yc.numel() // (n * n_out), n_out,
-                                  C.c_void_p(stats_d.data_ptr()))
-            _lib.check(rc, dev.ctx, 's3_chunk_stats')
-        del y
-        copy_stream = cls._copy_stream(dev)
-        stats_h = torch.empty(tuple(stats_d.shape), dtype=torch.float32,
-                              pin_memory=True)
-        ready = torch.cuda.Event()
-        ready.record()
-        with torch.cuda.stream(copy_stream):
-            copy_stream.wait_event(ready)
-            stats_h.copy_(stats_d, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(copy_stream)
-        stats_d.record_stream(copy_stream)
-        state = {'ticket': None, 'host': None}
-
-        def deliver():
-            """start the batch's device -> host DMA (idempotent).  The SDMA
-            engine is driven through ROCr (s3_dma_d2h_begin), which takes no
-            HIP event as a dependency: the host waits for the batch's forward
-            first — by the time ``iter_chunks`` calls this the NEXT batch is
-            already enqueued behind it, so the device does not idle."""
-            if not return_data or state['host'] is not None:
-                return
-            ready.synchronize()
-            host_ptr, host_arr = cls._delivery_buffer(
-                dev, tuple(yc.shape), lane)
-            state['host_ptr'] = host_ptr
-            ticket = C.c_uint64()
-            rc = -1
-            if options.sdma_delivery and not cls._sdma_refused:
-                rc = L.s3_dma_d2h_begin(
-                    dev.ctx, C.c_void_p(yc.data_ptr()), C.c_void_p(host_ptr),
-                    host_arr.size * 4, C.byref(ticket))
-                if rc != 0:
-                    # ROCr refused (no SDMA queue in this container, a foreign
-                    # allocator ...): say so once and copy through HIP instead
-                    logger.warning(
-                        'SDMA delivery unavailable (%s): falling back to '
-                        'hipMemcpyAsync for the chunk batches',
-                        _lib.last_error(dev.ctx))
-                    ForwardPass._sdma_refused = True
-            if rc != 0:
-                rc = L.s3_d2h_async(
-                    dev.ctx, C.c_void_p(yc.data_ptr()), C.c_void_p(host_ptr),
-                    host_arr.size * 4, C.c_void_p(copy_stream.cuda_stream))
-                _lib.check(rc, dev.ctx, 's3_d2h_async')
-                state['copy_ev'] = torch.cuda.Event()
-                state['copy_ev'].record(copy_stream)
-                ticket = None
-            state['ticket'], state['host'] = ticket, host_arr
-
-        def finish():
-            deliver()
-            ev.synchronize()
-            staged.clear()
-            if bias_counts is not None:
-                # (the batch has run: the reference's RuntimeError for QDM /
-                # PresRat results that are not finite)
-                bias_bc.check(bias_counts)
-            st = stats_h.numpy().reshape(n, 64, n_out, 3)
-            mn, mx = st[..., 0].min(1), st[..., 1].max(1)
-            nn = st[..., 2].sum(1)
-            skip, allowed = cls._const_ok(allowed_const)
-            fails = []
-            for k in range(n):
-                failed = False
-                if not skip:
-                    if nn[k].any():
-                        logger.error('Forward pass output contains NaN '
-                                     'values!')
-                        failed = True
-                    else:
-                        for i in range(n_out):
-                            if mn[k, i] == mx[k, i] and \
-                                    mn[k, i] not in allowed:
-                                logger.error('All values are the same for '
-                                             f'feature channel {i}!')
-                                failed = True
-                                break
-                fails.append(failed)
-            for k, chunk in enumerate(group):
-                if write and chunk.out_file is not None and not fails[k]:
-                    cls._write_chunk(chunk, model, yc[k], invert_uv, nn_fill,
-                                     meta, output_workers)
-            host_arr = state['host']
-            if state['ticket'] is not None:
-                rc = L.s3_dma_wait(dev.ctx, state['ticket'],
-                                   int(dev.comm_timeout_s * 1000))
-                state['ticket'] = None
-                if rc != 0:
-                    # the engine may still write into that buffer: it leaves
-                    # the ring for good (never reused, never freed)
-                    cls._retire_delivery_buffer(dev, tuple(yc.shape), lane,
-                                                state['host_ptr'])
-                _lib.check(rc, dev.ctx, 's3_dma_wait')
-            elif state.get('copy_ev') is not None:
-                state['copy_ev'].synchronize()
-            for k, chunk in enumerate(group):
-                # (a view into this generator's ring of delivery buffers:
-                # valid while the next ``d2h_ring - 2`` batches are yielded —
-                # batch k + d2h_ring claims the buffer of batch k when batch
-                # k + d2h_ring + 1 is enqueued, just before k + d2h_ring - 1
-                # is handed out)
-                yield (chunk, fails[k],
-                       host_arr[k] if host_arr is not None else None)
-        finish.deliver = deliver
-        return finish
+            out_file=chunk.out_file, meta_data=run.meta, invert_uv=False,
+            nn_fill=False, max_workers=run.output_workers, gids=chunk.gids)
 
     @classmethod
     def _exo_to_device(cls, dev, fields, rank4, keep, prep):
@@ -1507,9 +1115,6 @@ class ForwardPass:
         that are constant in time — the zero-stride views ``pad_source_data``
         builds from 3-D exo data — cross PCIe once and are laid over the
         time steps on the device (s3_broadcast_axis)"""
-        import ctypes as C
-
-        from . import _lib
         n = len(fields)
         const = all(f.ndim == 4 and f.shape[2] > 1 and f.strides[2] == 0
                     for f in fields)
@@ -1580,7 +1185,6 @@ class ForwardPass:
         the caller's arrays"""
         if exo is None:
             return None
-        from .utilities import ExoData
         if time_first:
             return ExoData({f: {'steps': [dict(st, data=np.transpose(
                 np.asarray(st['data']), (2, 0, 1, 3))) for st in e['steps']]}
@@ -1639,9 +1243,7 @@ class ForwardPass:
         """free the pinned delivery rings (up to ``d2h_ring`` x the batch's
         cropped output per output shape); views handed out earlier become
         invalid"""
-        from . import _lib
         from .engine import Device
-        import ctypes as C
         for (index, _, _), ring in list(cls._delivery.items()):
             dev = Device.get(index)
             for ptr, _arr in ring['bufs']:
@@ -1650,9 +1252,6 @@ class ForwardPass:
 
     @classmethod
     def _delivery_buffer(cls, dev, shape, lane=0):
-        import ctypes as C
-
-        from . import _lib
         key = (dev.index, shape, lane)
         ring = cls._delivery.setdefault(key, {'bufs': [], 'next': 0})
         if len(ring['bufs']) < cls.d2h_ring:
@@ -1779,3 +1378,459 @@ class ForwardPass:
             return self.run_batched(domain, out=out, writer=writer,
                                     batch=batch)
         return self.run_chunks(domain, out=out, writer=writer)
+
+
+class _ChunkBatch:
+    """One batch of equal-shaped chunks on the device chunk path of
+    ``iter_chunks``.  The constructor enqueues it stage by stage — route
+    decision, host inputs, input to device, chain walk, last forward, output
+    epilogue, statistics download; ``deliver()`` starts its device -> host
+    DMA, ``finish()`` waits for it and yields its ``(chunk, failed,
+    output_data)``.  A ``MultiStepGan`` chain runs step by step on the device;
+    a single model is a chain of one."""
+
+    def __init__(self, group, model, run):
+        self.group, self.model, self.run = group, model, run
+        self.n = len(group)
+        self.chain = hasattr(model, 'models')
+        self.steps = list(model.models) if self.chain else [model]
+        self.dev = self.steps[0]._gen.dev
+        self.exos = [e if e is None or isinstance(e, ExoData) else ExoData(e)
+                     for e in (chunk.exo_data for chunk in group)]
+        self.staged = []          # pinned upload buffers, alive until finish()
+        self.bias_bc = self.bias_counts = None
+        self.ticket = self.host = self.host_ptr = self.copy_ev = None
+        self._decide_route()
+        host = self._host_inputs()
+        #: input shape of the step being enqueued (the failure message's)
+        self.step_shape = self.in_shape
+        try:
+            xd = self._input_to_device(host)
+            xd, last_4d = self._walk_chain(xd)
+            y = self._last_forward(xd, last_4d)
+        except (AssertionError, _EnhancementMismatch):
+            raise
+        except Exception as e:
+            msg = 'Forward pass failed on chunk with shape {}.'.format(
+                self.step_shape)
+            logger.exception(msg)
+            raise RuntimeError(msg) from e
+        stats_d = self._epilogue(y, last_4d)
+        del y
+        self.copy_stream = ForwardPass._copy_stream(self.dev)
+        self.stats_h, self.ready, self.ev = _stats_to_host(
+            stats_d, self.copy_stream)
+
+    def _step_exo(self, exo, i):
+        """the exo entries model step ``i`` consumes (exo.py:108-130)"""
+        if exo is None or not self.chain:
+            return exo
+        return exo.get_model_step_exo(i)
+
+    def _upload(self, arr, dtype=np.float32):
+        return ForwardPass._upload_async(self.dev, arr, self.staged, dtype)
+
+    # -- stages, in the order the constructor runs them --------------------
+    def _decide_route(self):
+        """how the first step's input gets to the device (host logic only)"""
+        first, options = self.steps[0], self.run.options
+        self.first_4d = not getattr(first, 'is_5d', False)
+        # 4-D models: transpose + normalisation on the device
+        # (s3_chunk_time_first, numpy's arithmetic) unless the model brings
+        # its own norm_input
+        base_norm = _is_base_method(first, 'norm_input')
+        self.dev_norm = self.first_4d and options.device_norm_4d and \
+            not any(self._step_exo(e, 0) for e in self.exos) and base_norm
+        # chunks that carry a ``bias_correct`` record (raw input): corrected
+        # on the device — fused with the normalisation for a 5-D model, in
+        # place in front of s3_chunk_time_first for a 4-D one — unless the
+        # model normalises for itself or the batch is combined on the host
+        self.bias_dev = getattr(self.group[0], 'bias_correct', None) \
+            is not None
+        if self.bias_dev and not (
+                base_norm and (self.dev_norm or not self.first_4d) and
+                len(first.lr_features) <= _lib.BC_MAX_CHANNELS):
+            for chunk in self.group:
+                ForwardPass._bias_correct_host(chunk, self.model)
+            self.bias_dev = False
+
+    def _host_inputs(self):
+        """NaN check, then the batch's stacked host array: the raw chunks
+        ``(n, s1, s2, t, f)`` where the device normalises (``dev_norm``), the
+        raw chunks with their 'input' exo channels in the model's layout where
+        the bias-correction kernel does, the normalised model input otherwise.
+        Sets ``in_shape`` (the first step's input shape), ``n_t``, ``lr_t``."""
+        first, n, xs = self.steps[0], self.n, []
+        for chunk, exo in zip(self.group, self.exos):
+            # (one flat pass; the per-feature reduction over a (…, 2 .. 8)-wide
+            # last axis — 0.7 ms per 75 x 75 x 48 chunk — only when it found one)
+            if np.isnan(chunk.input_data).any():
+                mask = np.isnan(chunk.input_data).any(axis=(0, 1, 2))
+                feats = np.array(first.lr_features[:len(mask)])[mask]
+                msg = f'Input data for {feats} contains NaN values!'
+                logger.error(msg)
+                raise RuntimeError(msg)
+            exo0 = self._step_exo(exo, 0)
+            if self.dev_norm:
+                x = chunk.input_data
+            elif self.bias_dev or not self.first_4d:
+                x = first._combine_fwp_input(
+                    np.asarray(chunk.input_data)[None],
+                    ForwardPass._batch_axis(exo0))
+            else:
+                # (s1, s2, t, f) -> the t time steps as the batch of a 2-D
+                # model (``_reshape_data_chunk``, forward_pass.py:274-337)
+                # (contiguous: the normalisation below walks a transposed
+                # view four times slower)
+                x = first._combine_fwp_input(np.ascontiguousarray(np.transpose(
+                    np.asarray(chunk.input_data), (2, 0, 1, 3))),
+                    ForwardPass._batch_axis(exo0, time_first=True))
+            if not (self.dev_norm or self.bias_dev):
+                x = first.norm_input(x)
+            xs.append(np.asarray(x, dtype=np.float32))
+        if self.dev_norm:
+            host = np.stack(xs, axis=0)
+            self.in_shape = (n * host.shape[3], host.shape[1], host.shape[2],
+                             host.shape[4])
+        else:
+            host = np.concatenate(xs, axis=0) if n > 1 else xs[0]
+            self.in_shape = tuple(host.shape)
+        self.n_t = self.in_shape[0] // n          # 4-D: time steps per chunk
+        self.lr_t = self.n_t if self.first_4d else self.in_shape[3]
+        return host
+
+    def _input_stats(self):
+        """the first step's lo-res statistics as the device normalisation
+        takes them: ``(mean, std, stats_fp32)``, float64 arrays (None without
+        statistics) and whether the model holds them in float32"""
+        first = self.steps[0]
+        if first._means is None:
+            return None, None, 1
+        mu, sd = first._stats_for(first.lr_features)
+        if len(mu) != self.in_shape[-1]:
+            raise RuntimeError(
+                f'{len(mu)} normalisation statistics for '
+                f'{self.in_shape[-1]} input features')
+        sd = _nonzero_std(sd)
+        f32 = int(mu.dtype == np.float32 and sd.dtype == np.float32)
+        return (np.ascontiguousarray(mu, dtype=np.float64),
+                np.ascontiguousarray(sd, dtype=np.float64), f32)
+
+    def _input_to_device(self, host):
+        """plain upload of the normalised batch; or the raw batch through
+        ``bias_bc.correct`` (fused with the normalisation for a 5-D model)
+        and / or s3_chunk_time_first (4-D: time-major + normalisation)"""
+        if not (self.dev_norm or self.bias_dev):
+            return self._upload(host)
+        dev = self.dev
+        rawd = self._upload(host)
+        xd = dev.empty(self.in_shape)
+        if self.bias_dev:
+            self.bias_bc, windows = ForwardPass._device_bias(
+                self.group, self.steps[0], dev)
+        mu, sd, f32 = self._input_stats()
+
+        def upload(a):
+            return self._upload(a, a.dtype)
+        if not self.dev_norm:
+            # 5-D: correction + normalisation in one pass (s3_bias_correct)
+            _, self.bias_counts = self.bias_bc.correct(
+                rawd, windows, out=xd, mean=mu, std=sd, stats_fp32=f32,
+                upload=upload, keep=self.staged)
+            return xd
+        if self.bias_dev:
+            _, self.bias_counts = self.bias_bc.correct(
+                rawd, windows, upload=upload, keep=self.staged)
+        rc = _lib.lib().s3_chunk_time_first(
+            dev.ctx, _vp(rawd), self.n, _I64X3(*host.shape[1:4]),
+            self.in_shape[-1], _fptr(mu, _PD), _fptr(sd, _PD), f32, _vp(xd))
+        _lib.check(rc, dev.ctx, 's3_chunk_time_first')
+        return xd
+
+    def _layer_exo(self, i, ph, rank4):
+        """the 'layer' exo fields step ``i``'s generator consumes
+        mid-network, normalised, stacked over the batch, uploaded"""
+        m, out = self.steps[i], {}
+        for name in ph.input_names:
+            if name == 'x':
+                continue
+            fields = []
+            for exo in self.exos:
+                e = self._step_exo(exo, i)
+                assert e is not None and name in e, \
+                    f'the generator needs exogenous feature "{name}"'
+                fields.append(np.asarray(
+                    e.get_combine_type_data(name, 'layer')))
+            out[name] = ForwardPass._exo_to_device(
+                self.dev, fields, rank4, self.staged,
+                lambda a, name=name: m._reshape_norm_exo(
+                    tuple(a.shape), a, name))
+            # (the plan of a 2-D model carries a time axis of one)
+            want = tuple(int(v) for v in ph.in_shapes[name])
+            if tuple(v for v in out[name].shape if v != 1) == \
+                    tuple(v for v in want if v != 1):
+                out[name] = out[name].reshape(want)
+            if tuple(out[name].shape) != want:
+                raise RuntimeError(
+                    f'exogenous "{name}" of shape '
+                    f'{tuple(out[name].shape)} cannot be laid over '
+                    f'hi-res {want}')
+        return out
+
+    def _walk_chain(self, xd):
+        """every step but the last: plan forward + hand-over on the device.
+        Returns the last step's input and whether that step is 4-D."""
+        rank4 = self.first_4d
+        for i in range(len(self.steps) - 1):
+            ph = self.steps[i]._gen.plan(self.step_shape, training=False)
+            y = ph.forward(xd, self._layer_exo(i, ph, rank4))
+            xd, rank4 = self._hand_over(i, y, rank4)
+            del y
+            self.step_shape = tuple(int(v) for v in xd.shape)
+        return xd, rank4
+
+    def _hand_over(self, i, y, rank4):
+        """step i's normalised output -> step i + 1's normalised input
+        (multi_step.py:233-259) without leaving the device"""
+        m, nxt = self.steps[i], self.steps[i + 1]
+        nxt4 = not getattr(nxt, 'is_5d', False)
+        if rank4 and not nxt4:
+            y = self._time_last(y)
+        ysh = tuple(int(v) for v in y.shape)
+        produced = list(m.hr_out_features)
+        if len(produced) != ysh[-1]:
+            raise RuntimeError(
+                f'step {i} produced {ysh[-1]} channels for '
+                f'{len(produced)} output features')
+        wanted, names, exo_t = self._next_input_exo(i, produced, nxt4, ysh)
+        return self._step_handover(m, nxt, y, produced, wanted, names,
+                                   exo_t), nxt4
+
+    def _time_last(self, y):
+        """(n t, H, W, C) -> n samples (H, W, t, C)
+        (_transpose_model_input, multi_step.py:107-146)"""
+        dev, n, nt = self.dev, self.n, self.n_t
+        _, h, w, c = (int(v) for v in y.shape)
+        yt = dev.empty((n, h, w, nt, c))
+        rc = _lib.lib().s3_chunk_time_last(
+            dev.ctx, _vp(y), n, _I64X3(nt, h, w), _I64X3(0, 0, 0),
+            _I64X3(h, w, nt), c, None, None, _vp(yt))
+        _lib.check(rc, dev.ctx, 's3_chunk_time_last')
+        return yt
+
+    def _next_input_exo(self, i, produced, nxt4, ysh):
+        """what step ``i + 1`` takes from step ``i``'s output (``wanted``) and
+        from its 'input' exo fields (``names``, gathered over the batch and
+        uploaded: ``exo_t``, None without any)"""
+        nxt = self.steps[i + 1]
+        nxt_exo = [self._step_exo(e, i + 1) for e in self.exos]
+        wanted = [f for f in nxt.lr_features if f not in (nxt_exo[0] or {})]
+        missing = [f for f in wanted if f not in produced]
+        if missing:
+            raise ValueError(
+                f'step {i + 1} needs {missing}, step {i} only produces '
+                f'{produced}')
+        extra = len(nxt.lr_features) - len(wanted)
+        names = list(nxt.lr_features[-extra:]) if extra > 0 else []
+        if not names:
+            return wanted, names, None
+        fields = []
+        for e in nxt_exo:
+            absent = [f for f in names if f not in (e or {})]
+            assert not absent, (f'exogenous_data lacks {absent} '
+                                '(combine_type "input")')
+            cols = [np.asarray(e.get_combine_type_data(f, 'input'))
+                    for f in names]
+            fields.append(cols[0] if len(cols) == 1 else
+                          np.concatenate(cols, axis=-1))
+        exo_t = ForwardPass._exo_to_device(self.dev, fields, nxt4,
+                                           self.staged, lambda a: a)
+        if tuple(exo_t.shape[:-1]) != ysh[:-1]:
+            raise RuntimeError(
+                f'"input" exo of step {i + 1} has shape '
+                f'{tuple(exo_t.shape)}, the data {ysh}')
+        return wanted, names, exo_t
+
+    def _step_handover(self, m, nxt, y, produced, wanted, names, exo_t):
+        """s3_step_handover: un-normalise with ``m``'s statistics, pick the
+        ``wanted`` channels, append the exo channels, normalise with
+        ``nxt``'s"""
+        dev = self.dev
+        ysh = tuple(int(v) for v in y.shape)
+        scale, shift = _unnorm_affine(m)
+        mu = sd = None
+        if nxt._means is not None:
+            mu, sd = nxt._stats_for(nxt.lr_features)
+            sd = np.ascontiguousarray(_nonzero_std(sd), dtype=np.float32)
+            mu = np.ascontiguousarray(mu, dtype=np.float32)
+        cmap = (C.c_int32 * len(wanted))(*[produced.index(f) for f in wanted])
+        xn = dev.empty(ysh[:-1] + (len(wanted) + len(names),))
+        n_pos = int(np.prod(ysh[:-1], dtype=np.int64))
+        rc = _lib.lib().s3_step_handover(
+            dev.ctx, _vp(y), n_pos, ysh[-1], cmap, len(wanted), _fptr(scale),
+            _fptr(shift), _vp(exo_t) if exo_t is not None else None,
+            len(names), _fptr(mu), _fptr(sd), _vp(xn))
+        _lib.check(rc, dev.ctx, 's3_step_handover')
+        return xn
+
+    def _check_enhancement(self, yshape, last_4d):
+        """the enhancement checks of the reference (forward_pass.py:
+        _run_generator) on the last plan's output shape"""
+        model, in_shape = self.model, self.in_shape
+        if model.s_enhance * in_shape[1] != yshape[1]:
+            msg = ('The stated spatial enhancement of {}x did not match '
+                   'the low res / high res shapes of {} -> {}'.format(
+                       model.s_enhance, in_shape, yshape))
+            logger.error(msg)
+            raise _EnhancementMismatch(msg)
+        if model.t_enhance * self.lr_t != (self.n_t if last_4d
+                                           else yshape[3]):
+            msg = ('The stated temporal enhancement of {}x did not match '
+                   'the low res / high res shapes of {} -> {}'.format(
+                       model.t_enhance, in_shape, yshape))
+            logger.error(msg)
+            raise _EnhancementMismatch(msg)
+
+    def _last_forward(self, xd, last_4d):
+        """the last step's plan on ``xd``: enhancement checks, crop geometry
+        (``full``, ``cr``), the cropped batch ``yc``, then the forward —
+        returns the full-size output, or None where the window forward wrote
+        ``yc`` itself"""
+        last, dev = self.steps[-1], self.dev
+        ph = last._gen.plan(self.step_shape, training=False)
+        layer_exo = self._layer_exo(len(self.steps) - 1, ph, last_4d)
+        yshape = tuple(int(v) for v in ph.out_shape)
+        self._check_enhancement(yshape, last_4d)
+        self.n_out = yshape[-1]
+        self.scale, self.shift = _unnorm_affine(last)
+        # (4-D: the chunk's hi-res extents are (H, W, time steps))
+        self.full = (yshape[1], yshape[2], self.n_t) if last_4d \
+            else yshape[1:4]
+        self.cr = cr = ForwardPass._crop_bounds(self.group[0].hr_crop_slice,
+                                                self.full)
+        extent = tuple(b - a for a, b in cr)
+        self.yc = dev.empty((self.n,) + extent + (self.n_out,))
+        # halo crop + un-normalisation inside the tail conv (the window
+        # forward: no full-size output, halo positions of the last conv
+        # never computed) where the plan ends in the MFMA tail ...
+        self.windowed = self.run.options.window_forward and \
+            ph.supports_window and not last_4d
+        if not self.windowed:
+            return ph.forward(xd, layer_exo)
+        ph.forward_window(
+            xd, layer_exo, self.yc, [a for a, _ in cr], list(extent),
+            ForwardPass._affine_tensor(dev, self.scale, self.shift))
+        return None
+
+    def _epilogue(self, y, last_4d):
+        """un-normalisation, halo crop and the output check's statistics of
+        ``y`` into ``yc`` — same bits by every route; returns the device
+        statistics"""
+        dev, n, yc, n_out = self.dev, self.n, self.yc, self.n_out
+        lo = _I64X3(*(a for a, _ in self.cr))
+        extent = _I64X3(*(b - a for a, b in self.cr))
+        L = _lib.lib()
+        if last_4d:
+            # transpose to the chunk's (s1, s2, t) order + halo crop +
+            # un-normalisation in one pass, then the statistics
+            y1, y2, n_t = self.full
+            rc = L.s3_chunk_time_last(
+                dev.ctx, _vp(y), n, _I64X3(n_t, y1, y2), lo, extent, n_out,
+                _fptr(self.scale), _fptr(self.shift), _vp(yc))
+            _lib.check(rc, dev.ctx, 's3_chunk_time_last')
+            return _chunk_stats(dev, yc)
+        if self.windowed:
+            return _chunk_stats(dev, yc)
+        if _fused_epilogue_ok(n_out, extent[2], lo[2], self.full[2]):
+            # ... else all three in one pass over the cropped window
+            # (s3_chunk_epilogue) where the rows are 16-byte aligned ...
+            stats_d = dev.empty((n, 64, n_out, 3))
+            rc = L.s3_chunk_epilogue(
+                dev.ctx, _vp(y), n, _I64X3(*self.full), lo, extent, n_out,
+                _fptr(self.scale), _fptr(self.shift), _vp(yc), _vp(stats_d))
+            _lib.check(rc, dev.ctx, 's3_chunk_epilogue')
+            return stats_d
+        # ... the three separate kernels otherwise
+        _affine_channels(dev, y, self.scale, self.shift)
+        _crop_blocks(dev, y, self.cr, yc)
+        return _chunk_stats(dev, yc)
+
+    # -- after the enqueue --------------------------------------------------
+    def deliver(self):
+        """start the batch's device -> host DMA (idempotent).  The SDMA
+        engine is driven through ROCr (s3_dma_d2h_begin), which takes no
+        HIP event as a dependency: the host waits for the batch's forward
+        first — by the time ``iter_chunks`` calls this the NEXT batch is
+        already enqueued behind it, so the device does not idle."""
+        if not self.run.return_data or self.host is not None:
+            return
+        import torch
+        dev, yc, L = self.dev, self.yc, _lib.lib()
+        self.ready.synchronize()
+        self.host_ptr, host_arr = ForwardPass._delivery_buffer(
+            dev, tuple(yc.shape), self.run.lane)
+        ticket = C.c_uint64()
+        rc = -1
+        if self.run.options.sdma_delivery and not ForwardPass._sdma_refused:
+            rc = L.s3_dma_d2h_begin(
+                dev.ctx, _vp(yc), C.c_void_p(self.host_ptr),
+                host_arr.size * 4, C.byref(ticket))
+            if rc != 0:
+                # ROCr refused (no SDMA queue in this container, a foreign
+                # allocator ...): say so once and copy through HIP instead
+                logger.warning(
+                    'SDMA delivery unavailable (%s): falling back to '
+                    'hipMemcpyAsync for the chunk batches',
+                    _lib.last_error(dev.ctx))
+                ForwardPass._sdma_refused = True
+        if rc != 0:
+            rc = L.s3_d2h_async(
+                dev.ctx, _vp(yc), C.c_void_p(self.host_ptr),
+                host_arr.size * 4, C.c_void_p(self.copy_stream.cuda_stream))
+            _lib.check(rc, dev.ctx, 's3_d2h_async')
+            self.copy_ev = torch.cuda.Event()
+            self.copy_ev.record(self.copy_stream)
+            ticket = None
+        self.ticket, self.host = ticket, host_arr
+
+    def _wait_delivery(self):
+        dev = self.dev
+        if self.ticket is not None:
+            rc = _lib.lib().s3_dma_wait(dev.ctx, self.ticket,
+                                        int(dev.comm_timeout_s * 1000))
+            self.ticket = None
+            if rc != 0:
+                # the engine may still write into that buffer: it leaves
+                # the ring for good (never reused, never freed)
+                ForwardPass._retire_delivery_buffer(
+                    dev, tuple(self.yc.shape), self.run.lane, self.host_ptr)
+            _lib.check(rc, dev.ctx, 's3_dma_wait')
+        elif self.copy_ev is not None:
+            self.copy_ev.synchronize()
+
+    def finish(self):
+        """wait for the batch, check and write it, yield its ``(chunk,
+        failed, output_data)``"""
+        run = self.run
+        self.deliver()
+        self.ev.synchronize()
+        self.staged.clear()
+        if self.bias_counts is not None:
+            # (the batch has run: the reference's RuntimeError for QDM /
+            # PresRat results that are not finite)
+            self.bias_bc.check(self.bias_counts)
+        fails = _verdicts(
+            self.stats_h.numpy().reshape(self.n, 64, self.n_out, 3),
+            run.allowed_const, log=True)
+        for k, chunk in enumerate(self.group):
+            if run.write and chunk.out_file is not None and not fails[k]:
+                ForwardPass._write_chunk(chunk, self.model, self.yc[k], run)
+        self._wait_delivery()
+        for k, chunk in enumerate(self.group):
+            # (a view into this generator's ring of delivery buffers:
+            # valid while the next ``d2h_ring - 2`` batches are yielded —
+            # batch k + d2h_ring claims the buffer of batch k when batch
+            # k + d2h_ring + 1 is enqueued, just before k + d2h_ring - 1
+            # is handed out)
+            yield (chunk, fails[k],
+                   self.host[k] if self.host is not None else None)

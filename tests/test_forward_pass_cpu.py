@@ -488,3 +488,111 @@ def test_chunk_read_ahead_keeps_order_propagates_errors_and_stops():
     time.sleep(0.2)
     assert len(pulled) == n_pulled and n_pulled <= 8       # (depth 3 + in flight)
     assert threading.active_count() <= n0
+
+
+# -- the leaf steps the two device executors share (host halves) -------------
+def _slab_stats(y):
+    """``(n, c1, c2, c3, n_out)`` -> the ``(n, 64, n_out, 3)`` min / max /
+    NaN-count statistics in s3_chunk_stats' layout: position p of a chunk
+    falls into slab ``(p // 256) % 64``, NaNs are counted and left out of min
+    and max, a slab without values holds (+inf, -inf, 0)"""
+    n, n_out = y.shape[0], y.shape[-1]
+    flat = y.reshape(n, -1, n_out)
+    slab = (np.arange(flat.shape[1]) // 256) % 64
+    st = np.empty((n, 64, n_out, 3), np.float32)
+    st[..., 0], st[..., 1], st[..., 2] = np.inf, -np.inf, 0
+    for s in np.unique(slab):
+        part = flat[:, slab == s]
+        nan = np.isnan(part)
+        st[:, s, :, 0] = np.where(nan, np.inf, part).min(1)
+        st[:, s, :, 1] = np.where(nan, -np.inf, part).max(1)
+        st[:, s, :, 2] = nan.sum(1)
+    return st
+
+
+ALLOWED_CONST = [False, None, True, 0.75, 0.5, [0.5, 0.75], [0, 0.5], []]
+
+
+@pytest.mark.parametrize('n', [1, 3])
+@pytest.mark.parametrize('n_out', [1, 2, 3])
+@pytest.mark.parametrize('case', ['varied', 'nan_last', 'const'])
+def test_verdicts_agree_with_output_check(n, n_out, case):
+    """``_verdicts`` on the device statistics says per chunk what
+    ``_output_check`` says on the data, for every form of ``allowed_const``"""
+    from sup3r_amd.forward_pass import _verdicts
+    rng = np.random.default_rng(100 * n + 10 * n_out + len(case))
+    # 5 * 4 * 70 = 1400 positions: five full slabs of 256 and a partial one
+    y = rng.standard_normal((n, 5, 4, 70, n_out)).astype(np.float32)
+    if case == 'nan_last':
+        y[-1, -1, -1, -1, -1] = np.nan
+    elif case == 'const':
+        y[n // 2, ..., n_out - 1] = np.float32(0.75)
+    stats = _slab_stats(y)
+    expect_any = False
+    for allowed in ALLOWED_CONST:
+        want = [ForwardPass._output_check(y[k], allowed) for k in range(n)]
+        assert _verdicts(stats, allowed) == want, (allowed, want)
+        expect_any = expect_any or any(want)
+    # the cases do what they are named for
+    assert expect_any == (case != 'varied')
+    if case == 'nan_last':
+        assert _verdicts(stats, False) == [False] * (n - 1) + [True]
+    if case == 'const':
+        hit = [k == n // 2 for k in range(n)]
+        assert _verdicts(stats, 0.5) == hit == _verdicts(stats, [0, 0.5])
+        assert not any(_verdicts(stats, 0.75))
+        assert not any(_verdicts(stats, [0.5, 0.75]))
+    assert _verdicts(stats, True) == [False] * n
+
+
+def _axis_slices(n):
+    a, b = 2, 3
+    return [slice(None), slice(a, None), slice(None, -b), slice(a, -b),
+            slice(a, n - b)]
+
+
+def test_crop_bounds_equal_plain_slicing():
+    """``_crop_bounds`` against numpy's own slicing: extents and start
+    offsets, every None / negative-stop form per axis, and the ``hr_crop`` of
+    a slicer's first, an interior and its last chunk"""
+    import itertools
+    shape = (9, 12, 10)
+    crops = [tuple(c) for c in itertools.product(
+        *[_axis_slices(n) for n in shape])]
+    sl = ChunkSlicer((14, 11), 13, 2, 4, (6, 5, 6), spatial_pad=2,
+                     temporal_pad=2)
+    cases = [(c, shape) for c in crops]
+    for idx in (0, sl.n_chunks // 2, sl.n_chunks - 1):
+        c = sl.chunks[idx]
+        lr = [s_.stop - s_.start + lo + hi for s_, (lo, hi) in
+              zip(c['lr_pad_slice'], c['pad_width'])]
+        cases.append((tuple(c['hr_crop']),
+                      (2 * lr[0], 2 * lr[1], 4 * lr[2])))
+    assert len(cases) == 5 ** 3 + 3
+    for crop, shp in cases:
+        got = ForwardPass._crop_bounds(crop, shp)
+        assert tuple(b - a for a, b in got) == np.empty(shp)[crop].shape
+        for (a, b), s_, n in zip(got, crop, shp):
+            kept = np.arange(n)[s_]
+            assert (a, b) == (kept[0], kept[-1] + 1)
+
+
+# (n_out, crop extent c3, crop start, full extent y3) along the last axis ->
+# s3_chunk_epilogue may run: n_out divides 1024 and is at most 16, and every
+# one of the three, times n_out, is a multiple of 4 floats (16 bytes)
+FUSED_TABLE = [
+    (1, 8, 4, 12, True), (1, 8, 0, 12, True),
+    (1, 7, 4, 12, False), (1, 8, 3, 12, False), (1, 8, 4, 10, False),
+    (2, 6, 2, 10, True), (2, 6, 0, 10, True),
+    (2, 7, 2, 10, False), (2, 6, 1, 10, False), (2, 6, 2, 9, False),
+    (3, 8, 4, 12, False), (3, 7, 3, 9, False),        # 1024 % 3 != 0
+    (4, 7, 3, 9, True), (4, 8, 4, 12, True),
+    (16, 5, 1, 7, True),
+    (32, 8, 4, 12, False), (32, 5, 1, 7, False),      # more than 16 channels
+]
+
+
+@pytest.mark.parametrize('n_out,c3,lo3,y3,want', FUSED_TABLE)
+def test_fused_epilogue_predicate(n_out, c3, lo3, y3, want):
+    from sup3r_amd.forward_pass import _fused_epilogue_ok
+    assert _fused_epilogue_ok(n_out, c3, lo3, y3) is want

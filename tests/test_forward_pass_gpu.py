@@ -1010,3 +1010,58 @@ def test_window_forward_equals_full_forward_then_crop(temporal_pad):
             scale = np.abs(ref[i]).max()
             assert np.abs(got[i] - ref[i]).max() < 2e-6 * scale
     assert np.abs(ref[ids[0]]).max() > 0
+
+
+def test_three_kernel_epilogue_through_iter_chunks():
+    """the un-fused output epilogue of ``iter_chunks`` (s3_affine_channels ->
+    s3_copy_block per chunk -> s3_chunk_stats) against ``run_generator`` on
+    the same chunks, bit for bit.  Two (8, 8, 6, 3) chunks and a shorter last
+    one: a batch of two and a batch of one."""
+    # How this configuration gets to the three kernels (read off the epilogue
+    # before it was split into stages, where this was the last ``else`` of
+    # ``if is_4d / elif windowed / elif fused``, and off ``_ChunkBatch.
+    # _epilogue`` now): the model is 5-D, so not the time-last transpose-crop;
+    # ``window_forward=False``, so not the window forward; three output
+    # features, and ``fused`` starts with ``1024 % n_out == 0``, so not
+    # s3_chunk_epilogue, whatever the rows' alignment.
+    from sup3r_amd import ForwardPass, Sup3rGan
+    from sup3r_amd.forward_pass import register_model
+    from sup3r_amd.strategy import ArrayStrategy
+    feats = ['u_10m', 'v_10m', 'temperature_2m']
+    Sup3rGan.seed(6)
+    means = {f: np.float32(0.2 * (i + 1)) for i, f in enumerate(feats)}
+    stds = {f: np.float32(1.25 + 0.5 * i) for i, f in enumerate(feats)}
+    spec = json.load(open(os.path.join(CFG, 'test_gen_st_2x_4x_2f.json')))
+    tail = [layer for layer in spec['hidden_layers']
+            if layer.get('filters') == 2]
+    assert len(tail) == 1
+    tail[0]['filters'] = 3
+    m = Sup3rGan(spec, os.path.join(CFG, 'test_disc_st_same.json'),
+                 means=means, stdevs=stds)
+    m.set_model_params(lr_features=feats, hr_out_features=feats, s_enhance=2,
+                       t_enhance=4)
+    m.init_weights((1, 8, 8, 6, 3), (1, 16, 16, 24, 3))
+    assert m.is_5d and len(m.hr_out_features) == 3 and 1024 % 3 != 0
+    rng = np.random.default_rng(31)
+    domain = (rng.standard_normal((4, 4, 11, 3)) * 2 + 0.5).astype(np.float32)
+    register_model('Sup3rGan', {'model_dir': 'three-kernel'}, m)
+    st = ArrayStrategy(domain, {'model_dir': 'three-kernel'}, (4, 4, 4),
+                       spatial_pad=2, temporal_pad=1, max_nodes=1, model=m)
+    fwp = ForwardPass(st, 0)
+    ids = [int(i) for i in st.node_chunks[0]]
+    chunks = [fwp.get_input_chunk(i) for i in ids]
+    shapes = [tuple(c.input_data.shape) for c in chunks]
+    assert shapes[:2] == [(8, 8, 6, 3)] * 2 and len(shapes) == 3 and \
+        shapes[2] != shapes[0]
+    assert ForwardPass._device_path(m, chunks[0])
+    ref = [ForwardPass.run_generator(
+        c.input_data, c.hr_crop_slice, m, s_enhance=2, t_enhance=4)
+        for c in (fwp.get_input_chunk(i) for i in ids)]
+    got = [(c.index, failed, np.array(d)) for c, failed, d in
+           ForwardPass.iter_chunks(chunks, m, batch=2,
+                                   options={'window_forward': False})]
+    assert [g[0] for g in got] == ids and not any(g[1] for g in got)
+    for (_, _, d), r in zip(got, ref):
+        assert d.shape == r.shape and d.shape[-1] == 3
+        np.testing.assert_array_equal(d, r)
+    assert np.abs(ref[0]).max() > 0
