@@ -633,6 +633,30 @@ int s3_condmom_target(s3_ctx* ctx, const float* hr, const float* lr, const float
                       unsigned flags, int s_pad, int t_lo, int t_hi, float* out,
                       float* mask);
 
+/* ---- training samples out of a resident data cube ---------------------------
+ * replaces the host slicing of Sampler.__next__ (sup3r/preprocessing/samplers/
+ * base.py:228-262: _fast_batch's one box of batch_size * t steps reshaped,
+ * _slow_batch's batch_size boxes stacked) and the upload of the batch:
+ *   data (S1, S2, T, C) fp32, the container layout, resident on the device;
+ *        offsets into it are 64-bit (a year of a 100 x 100 domain with 10
+ *        features is 3.5 GB)
+ *   origins_host[n][3]  host: i0, j0, k0 of every sample's box (s1, s2, t)
+ *   channel_host[c_out] host: the cube channel of every channel kept
+ *   out[m, i, j, k, q] = data[i0[m] + i, j0[m] + j, k0[m] + k, channel[q]],
+ *        (n, s1, s2, t, c_out); a copy: every bit pattern arrives as it is.
+ * Origins and channel map travel in the kernel arguments, S3_SAMPLE_MAX_ORIGINS
+ * samples per launch (a larger n is split here); nothing is copied to the
+ * device and nothing synchronises: the launches are asynchronous on the
+ * context's stream.
+ * S3_EINVAL, before anything is launched: a box that leaves the cube, a
+ * channel outside [0, C), extents or n below 1, c_out above
+ * S3_SAMPLE_MAX_CHANNELS, 2^31 or more elements of out. */
+#define S3_SAMPLE_MAX_ORIGINS 64
+#define S3_SAMPLE_MAX_CHANNELS 32
+int s3_sample_gather(s3_ctx* ctx, const float* data, int64_t S1, int64_t S2, int64_t T, int C,
+                     const int* origins_host, int n, int s1, int s2, int t,
+                     const int* channel_host, int c_out, float* out);
+
 /* ---- bias correction of forward-pass chunks on the device ------------------
  * replaces the host numpy / rex of ForwardPassStrategy.prep_chunk_data
  * (sup3r/pipeline/strategy.py:502-517 -> bias_correct_features ->

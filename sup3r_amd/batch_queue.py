@@ -15,7 +15,10 @@ with its own machinery:
   ``queue.Queue`` until told to stop — no TensorFlow anywhere;
 * coarsening + smoothing (``SingleBatchQueue.transform``) run on the GPU
   (:class:`~sup3r_amd.batch_transform.DeviceBatchTransform`) when a batch is
-  handed out, so what the training loop receives are device tensors.
+  handed out, so what the training loop receives are device tensors;
+* over samplers whose data lives on the device (samplers.py) there is no
+  thread at all: the batch is drawn — one gather launch — when it is handed
+  out.
 
 Samplers are duck-typed the way the reference uses them: ``features``,
 ``sample_shape`` (hi-res s1, s2, t), ``batch_size``, optional ``size``
@@ -66,12 +69,17 @@ class DsetTuple(dict):
         return dict(self.items())
 
 
+def _as_array(a):
+    return a if getattr(a, 'is_cuda', False) else np.asarray(a)
+
+
 def _as_arrays(raw):
     """a sampler's return value (an array, or a tuple of them for dual
-    samplers) as numpy"""
+    samplers) as numpy; what a device-resident sampler hands out (samplers.py)
+    is a device tensor already and stays one"""
     if isinstance(raw, tuple):
-        return tuple(np.asarray(a) for a in raw)
-    return np.asarray(raw)
+        return tuple(_as_array(a) for a in raw)
+    return _as_array(raw)
 
 
 class _Feeder:
@@ -169,8 +177,12 @@ class DeviceBatchQueue:
         self.container_index = 0
         self.timer = Timer()
         self._check_samplers()
+        # nothing to prefetch from samplers whose data is on the device: a
+        # draw is index arithmetic plus one asynchronous launch, and a
+        # context serves one host thread at a time — the consumer's
+        on_demand = mode == 'eager' or self.device_resident
         self._feeder = _Feeder(self.sample_batch,
-                               0 if mode == 'eager' else self.queue_cap,
+                               0 if on_demand else self.queue_cap,
                                thread_name, self.max_workers)
         self._thread_name = thread_name
 
@@ -217,6 +229,12 @@ class DeviceBatchQueue:
             return list(ind)
         feats = self.features
         return [feats.index(f) for f in self.hr_features]
+
+    @property
+    def device_resident(self):
+        """every sampler holds its data on the device (samplers.py)"""
+        return all(getattr(c, 'device_resident', False)
+                   for c in self.containers)
 
     @property
     def container_weights(self):
@@ -275,7 +293,8 @@ class DeviceBatchQueue:
 
     def start(self):
         """Keep the FIFO of raw batches full from now on (no-op in eager
-        mode and for ``queue_cap`` 0: batches are then drawn on demand)."""
+        mode, for ``queue_cap`` 0 and over device-resident samplers: batches
+        are then drawn on demand)."""
         self._feeder.start()
 
     def stop(self):

@@ -273,6 +273,26 @@ __host__ __device__ inline int s3_reflect(int i, int n) {
   return i;
 }
 
+// floor(x / d) for every 32-bit x as a multiply-high and two shifts
+// (Granlund & Montgomery 1994, fig. 4.1): built on the host for a divisor known
+// at launch time, passed by value, applied by the index arithmetic of the
+// streaming kernels (kernels_condmom.hip, kernels_sample.hip)
+struct FastDiv {
+  uint32_t d = 1, m = 1, sh1 = 0, sh2 = 0;
+  FastDiv() = default;
+  explicit FastDiv(uint32_t div) : d(div) {
+    uint32_t l = 0;
+    while (l < 32 && ((uint64_t)1 << l) < div) ++l;        // ceil(log2 d)
+    m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - div)) / div + 1);
+    sh1 = l < 1 ? l : 1;
+    sh2 = l < 1 ? 0 : l - 1;
+  }
+  __device__ __forceinline__ uint32_t operator()(uint32_t x) const {
+    const uint32_t t = __umulhi(m, x);
+    return (t + ((x - t) >> sh1)) >> sh2;
+  }
+};
+
 // XCD-aware tile order for one-tile-per-workgroup kernels: the dispatcher puts
 // block b on XCD b % 8 and every XCD has a private L2, so hand each XCD a
 // contiguous run of tiles (bijective on [0, nblk)): neighbouring tiles share

@@ -22,25 +22,8 @@ namespace {
 constexpr int kBlk = 256;
 constexpr int kMaxC = 32;
 
-// floor(x / d) for every 32-bit x as a multiply-high and two shifts
-// (Granlund & Montgomery 1994, fig. 4.1): the index arithmetic of a vector is
-// six divisions by run-time constants
-struct FastDiv {
-  uint32_t d = 1, m = 1, sh1 = 0, sh2 = 0;
-  FastDiv() = default;
-  explicit FastDiv(uint32_t div) : d(div) {
-    uint32_t l = 0;
-    while (l < 32 && ((uint64_t)1 << l) < div) ++l;        // ceil(log2 d)
-    m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - div)) / div + 1);
-    sh1 = l < 1 ? l : 1;
-    sh2 = l < 1 ? 0 : l - 1;
-  }
-  __device__ __forceinline__ uint32_t operator()(uint32_t x) const {
-    const uint32_t t = __umulhi(m, x);
-    return (t + ((x - t) >> sh1)) >> sh2;
-  }
-};
-
+// (the index arithmetic of a vector is six divisions by run-time constants:
+// FastDiv, common.h)
 struct CmGeom {
   uint32_t total;                 // elements of hr
   uint32_t S1, S2, T, C;          // hr extents (n is implied)
