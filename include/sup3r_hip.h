@@ -511,6 +511,34 @@ int s3_broadcast_axis(s3_ctx* ctx, const float* src, int64_t outer, int64_t a, i
 int s3_step_handover(s3_ctx* ctx, const float* y, int64_t n_pos, int c_src, const int* map_host,
                      int c_sel, const float* scale_host, const float* shift_host, const float* exo,
                      int n_exo, const float* mean_host, const float* std_host, float* x);
+/* the hand-over with TWO sources: the join of SolarMultiStepGan's spatial
+ * branches (sup3r/models/multi_step.py:785-806).  ya = (t, h, w, ca) and yb =
+ * (t, h, w, cb) are the NORMALISED, time-first outputs of the two branches'
+ * last 2-D generators; x = (1, h, w, t, na + nb) is the normalised input of the
+ * temporal chain: x[0,i,j,s,k] = norm(unnorm_a(ya[s,i,j,map_a[k]])) for k < na,
+ * norm(unnorm_b(yb[s,i,j,map_b[k - na]])) for the rest — unnorm = v *
+ * scale[src channel] + shift[src channel] (two fp32 roundings), norm = (v -
+ * mean[k]) / std[k] per destination channel, as in s3_step_handover; NULL
+ * scale / shift of a source: no un-normalisation of it; NULL mean / std: no
+ * normalisation.  Every bit pattern takes the same arithmetic.  Maps and
+ * statistics travel in the kernel arguments (no upload, no synchronisation);
+ * 64-bit offsets; any t, h, w >= 1.  S3_EINVAL unless ca, cb, na + nb <= 16
+ * and na + nb >= 1 (na or nb may be 0: that source is not read). */
+int s3_branch_join(s3_ctx* ctx, const float* ya, int ca, const int* map_a_host, int na,
+                   const float* scale_a_host, const float* shift_a_host,
+                   const float* yb, int cb, const int* map_b_host, int nb,
+                   const float* scale_b_host, const float* shift_b_host,
+                   int64_t t, int64_t h, int64_t w,
+                   const float* mean_host, const float* std_host, float* x);
+/* SolarMultiStepGan.temporal_pad (multi_step.py:824-852) fused with
+ * un_norm_output: y = (outer, t, c) -> out = (outer, t + 2 pad, c), out[o, i, q]
+ * = unnorm(y[o, r(i - pad), q]) with r numpy's mode='reflect' for ANY pad
+ * width: p = 2 (t - 1), m = ((j mod p) + p) mod p, r(j) = m if m < t else p - m;
+ * r = 0 for t = 1.  c <= 16; NULL scale / shift: a pure pad; pad = 0: the
+ * un-normalisation alone. */
+int s3_time_pad_reflect(s3_ctx* ctx, const float* y, int64_t outer, int64_t t, int c,
+                        int64_t pad, const float* scale_host, const float* shift_host,
+                        float* out);
 /* the same hand-over for a 2-D (spatial) model, whose batch axis is the chunk's
  * time axis (ForwardPass._reshape_data_chunk, sup3r/pipeline/forward_pass.py:
  * 274-337: np.transpose(data_chunk, (2, 0, 1, 3)) in, np.transpose(hi_res, (1,

@@ -17,7 +17,8 @@ from .solar_cc import SolarCC  # noqa: E402,F401
 from .with_obs import Sup3rGanWithObs  # noqa: E402,F401
 from .forward_pass import (ChunkPathOptions, ChunkSlicer,  # noqa: E402,F401
                            ForwardPass)
-from .multi_step import MultiStepGan, MultiStepSurfaceMetGan  # noqa: E402,F401
+from .multi_step import (MultiStepGan, MultiStepSurfaceMetGan,  # noqa: E402,F401
+                         SolarMultiStepGan)
 from .linear import LinearInterp  # noqa: E402,F401
 from .surface import SurfaceSpatialMetModel  # noqa: E402,F401
 from .batch_queue import (DeviceBatchHandler, DeviceBatchQueue,  # noqa: E402,F401
@@ -35,7 +36,7 @@ from . import batch_queue_dual as _dual  # noqa: E402
 from .batch_queue_dual import *  # noqa: E402,F401,F403
 
 __all__ = ['Sup3rGan', 'Sup3rCondMom', 'Sup3rGanDC', 'SolarCC', 'Sup3rGanWithObs', 'MultiStepGan',
-           'MultiStepSurfaceMetGan', 'LinearInterp', 'SurfaceSpatialMetModel', 'ForwardPass', 'ChunkPathOptions',
+           'MultiStepSurfaceMetGan', 'SolarMultiStepGan', 'LinearInterp', 'SurfaceSpatialMetModel', 'ForwardPass', 'ChunkPathOptions',
            'ChunkSlicer', 'BiasParams', 'DeviceBiasCorrection', 'global_linear_bc', 'local_linear_bc',
            'monthly_local_linear_bc', 'local_qdm_bc', 'local_presrat_bc', 'DeviceBatchQueue', 'DeviceBatchHandler', 'DsetTuple',
            *_cond.__all__, *_samplers.__all__, *_dc.__all__, *_dual.__all__, '__version__']

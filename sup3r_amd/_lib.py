@@ -46,7 +46,8 @@ EXPORTS = [
     's3_sample_gather',
     's3_st_interp', 's3_resize2d', 's3_surface_downscale',
     's3_chunk_epilogue', 's3_chunk_time_last', 's3_chunk_time_first',
-    's3_step_handover', 's3_broadcast_axis',
+    's3_step_handover', 's3_broadcast_axis', 's3_branch_join',
+    's3_time_pad_reflect',
     's3_host_register', 's3_host_unregister', 's3_d2h_window',
     's3_d2h_stream', 's3_host_alloc', 's3_host_free', 's3_d2h_async',
     's3_dma_d2h_begin', 's3_dma_wait',
@@ -210,6 +211,11 @@ def lib():
         's3_broadcast_axis': (i32, [vp, vp, i64, i64, i64, i64, vp]),
         's3_step_handover': (i32, [vp, vp, i64, i32, C.POINTER(i32), i32, pf,
                                    pf, vp, i32, pf, pf, vp]),
+        's3_branch_join': (i32, [vp, vp, i32, C.POINTER(i32), i32, pf, pf,
+                                 vp, i32, C.POINTER(i32), i32, pf, pf, i64,
+                                 i64, i64, pf, pf, vp]),
+        's3_time_pad_reflect': (i32, [vp, vp, i64, i64, i32, i64, pf, pf,
+                                      vp]),
         's3_chunk_time_last': (i32, [vp, vp, i32, C.POINTER(i64),
                                      C.POINTER(i64), C.POINTER(i64), i32, pf,
                                      pf, vp]),

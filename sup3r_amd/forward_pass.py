@@ -855,6 +855,12 @@ class ForwardPass:
         else (``MultiStepGan``, 'output' exo) takes ``run_generator`` ->
         ``model.generate`` chunk by chunk"""
         options = _opts(options)
+        from .multi_step import SolarMultiStepGan
+        if isinstance(model, SolarMultiStepGan):
+            # two branches and a join: its ``models`` (wind + temporal steps,
+            # what the enhancement factors come from) are NOT a linear chain.
+            # Chunk by chunk through its ``generate``, device resident inside
+            return False
         steps = getattr(model, 'models', None)
         if steps is not None:
             return cls._device_chain(model, chunk, options)

@@ -1,7 +1,7 @@
 """Small host utilities the model API relies on (counterparts of
 sup3r/utilities/utilities.py ``Timer`` :261-335, ``camel_to_underscore``,
-``safe_cast`` :140-152, and ``ExoData.get_combine_type_data``,
-sup3r/preprocessing/data_handlers/exo.py:54-224)."""
+``safe_cast`` :140-152, and ``ExoData.get_combine_type_data`` /
+``ExoData.split``, sup3r/preprocessing/data_handlers/exo.py:54-224)."""
 import logging
 import re
 import time
@@ -114,6 +114,27 @@ class ExoData(dict):
             if steps:
                 out[feature] = {'steps': steps}
         return ExoData(out)
+
+    def split(self, split_steps):
+        """One ``ExoData`` per range of model steps (exo.py:144-193): the steps
+        with ``min_step <= model < max_step`` go to part i, their ``model``
+        counted from ``min_step``; a feature without a step in a part is
+        absent from it.  ``[len(spatial_models)]`` splits the steps of a
+        spatial chain from those of the temporal chain behind it.  The step
+        dicts are COPIED: this object (a chunk's exo data, split again on the
+        next call) keeps its model indices."""
+        split_steps = list(split_steps)
+        n_parts = len(split_steps) + 1
+        bounds = [0, *split_steps] if split_steps[0] != 0 else split_steps
+        parts = [{} for _ in range(n_parts)]
+        for feature, entry in self.items():
+            for i, lo in enumerate(bounds):
+                hi = None if lo == bounds[-1] else bounds[i + 1]
+                steps = [dict(s, model=s['model'] - lo) for s in entry['steps']
+                         if lo <= s['model'] and (hi is None or s['model'] < hi)]
+                if steps:
+                    parts[i][feature] = {'steps': steps}
+        return [ExoData(p) for p in parts]
 
     def get_combine_type_data(self, feature, combine_type, model_step=None):
         steps = self[feature]['steps']
