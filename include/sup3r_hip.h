@@ -102,7 +102,7 @@ enum { S3_STAT_PERSIST_DGRAD = 0, /* trunk data gradients on the persistent kern
        S3_STAT_DGRAD_C2_SLIDE = 3, /* first-layer data gradients on the sliding kernel */
        S3_STAT_BUCKETS = 4,       /* bucket collectives issued under backward passes */
        S3_STAT_ALLREDUCES = 5,    /* whole-buffer / scalar all-reduces issued        */
-       /* support passes of the training step (kernels_misc.hip), one per kernel launched */
+       /* support passes of the training step (kernels_reduce / _pointwise / _fold.hip), one per kernel launched */
        S3_STAT_BIAS_STAGE1 = 6,     /* bias gradient: one channel per lane (bias_grad_stage1)   */
        S3_STAT_BIAS_STAGE1_V4 = 7,  /* bias gradient: four channels per lane (bias_grad_stage1_v4) */
        S3_STAT_BIAS_COLS = 8,       /* bias gradient: > 256 channels, one serial walk per channel */

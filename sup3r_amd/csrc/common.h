@@ -586,13 +586,28 @@ int launch_conv_fewpos_wgrad_mfma(s3_ctx* ctx, const ConvGeom& g, const float* x
 
 int launch_gather(s3_ctx* ctx, const GatherGeom& g, const void* in, void* out,
                   int esize);
-// (frame16: dout is a bf16 frame — float4-fold geometries only)
-int launch_gather_bwd(s3_ctx* ctx, const GatherGeom& g, const float* dout,
-                      float* din, void* side16 = nullptr, int frame16 = 0);
+// Adjoint of a gather op: din = fold(frame) — of a pad over a whole frame (the
+// padded-frame data gradient of a conv) with what the plan can fuse into the
+// store.  gather_bwd_mask_ok(g): the 4 / 8 channels-per-lane walks, the only
+// ones that take a bf16 frame, a mode other than PLAIN or a bf16 store.
+struct FoldJob {
+  const void* frame = nullptr;         // dout, fp32 or ...
+  bool frame16 = false;                // ... bf16
+  float* din = nullptr;
+  bool out_bf16 = false;               // bf16-ONLY store (din is then a bf16 buffer; MASKED)
+  unsigned short* side16 = nullptr;    // fp32 store + bf16 copy (PLAIN, ADD)
+  enum Mode { PLAIN, MASKED, ADD } mode = PLAIN;
+  // MASKED: y of the producer conv (fp32 or bf16), whose activation adjoint
+  // (1 where y > 0, else slope) multiplies the fold; ADD: the fp32 first
+  // gradient contribution the fold is added to
+  const void* aux = nullptr;
+  bool aux_bf16 = false;
+  float slope = 0.f;
+  float* bsum = nullptr;               // MASKED, ADD: channel sums of din, partial[block][C] (gather_bwd_bsum_ok)
+};
+// (a job the kernels have no instantiation for is S3_EINVAL and launches nothing)
+int launch_fold(s3_ctx* ctx, const GatherGeom& g, const FoldJob& job);
 bool gather_bwd_mask_ok(const GatherGeom& g);
-int launch_gather_bwd_masked(s3_ctx* ctx, const GatherGeom& g, const float* dout, float* din,
-                             const void* mask_y, int y_bf16, float slope, float* bsum = nullptr,
-                             int out_bf16 = 0, int frame16 = 0);
 int launch_act(s3_ctx* ctx, const float* x, float* y, int64_t n, int act,
                float alpha);
 // dx = dy * act'(y)  (y is the activation OUTPUT; sign-preserving acts only)
@@ -609,8 +624,6 @@ int launch_add16(s3_ctx* ctx, const void* a, const void* b, void* y, int64_t n);
 int launch_add(s3_ctx* ctx, const float* a, const float* b, float* y, int64_t n,
                int c, int bcast_c);
 int launch_axpy(s3_ctx* ctx, const float* x, float* y, int64_t n);  // y += x
-int launch_gather_bwd_add(s3_ctx* ctx, const GatherGeom& g, const float* dout, float* din, const float* add,
-                          float* bsum = nullptr, void* side16 = nullptr, int frame16 = 0);
 bool gather_bwd_bsum_ok(const GatherGeom& g);
 int gather_bwd_bsum_blocks(const s3_ctx* ctx, const GatherGeom& g);
 int launch_bias_grad_from_partial(s3_ctx* ctx, const float* partial, int nblk, int c, float* db, int accumulate,
@@ -654,6 +667,9 @@ int launch_fill(s3_ctx* ctx, float* p, int64_t n, float v);
 extern "C" S3_INTERNAL int s3_comm_reduce_range(s3_ctx* ctx, float* buf, int64_t n);
 extern "C" S3_INTERNAL int s3_params_take_armed(s3_params* p, int* n_buckets);
 int launch_mean_abs(s3_ctx* ctx, const float* p, int64_t n, float* out_dev);
+// out[0] (+)= scale * sum of partial[0 .. nblk): stage 2 of the scalar
+// reductions; the caller's hipGetLastError covers it
+void launch_sum_stage2(s3_ctx* ctx, const float* partial, int nblk, float scale, float* out, int accumulate);
 int ensure_scratch(s3_ctx* ctx, size_t bytes);
 
 // whole-network kernel for small 2-D conv stacks (kernels_fused2d.hip)

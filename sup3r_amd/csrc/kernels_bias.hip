@@ -20,7 +20,7 @@
 //     one or two time windows): a row comes from HBM once and is reused from
 //     the cache by that pixel's time steps;
 //   * optionally the result is written normalised, (x - mean) / std, with the
-//     arithmetic of s3_chunk_time_first (kernels_misc.hip).
+//     arithmetic of s3_chunk_time_first (kernels_chunk_io.hip).
 // Non-finite results are counted per channel: lanes count in a register, the
 // wave sums by shuffles and issues one integer atomic — only if it met one.
 // No float atomics.

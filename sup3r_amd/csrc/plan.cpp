@@ -2367,6 +2367,13 @@ static bool fold_side16_ok(const s3_plan* pl, const OpRec& o, int rin) {
   return po.use16 && po.cg.act == S3_ACT_NONE && po.cg.d2s <= 1 && (po.cg.Cout & 3) == 0;
 }
 
+// the adjoint of a gather op, or the fold of an fp32 frame, with nothing fused
+static int fold_plain(s3_ctx* ctx, const GatherGeom& g, const float* dout, float* din) {
+  FoldJob job;
+  job.frame = dout; job.din = din;
+  return launch_fold(ctx, g, job);
+}
+
 // Backward of conv i in stages — dPre, bias + weight gradient, data gradient
 // (+ the fold of its frame) — that hand each other `dp` and nothing else;
 // what outlives the conv is in pl->bw.
@@ -2560,6 +2567,8 @@ struct ConvBwd {
       bs = pl->bsum;
       bw.claim_bsum(rin, gather_bwd_bsum_blocks(ctx, fg));
     }
+    FoldJob job;
+    job.frame = pl->dxp; job.frame16 = frame16 != 0; job.din = out;
     if (!fuse) {
       // second contribution to a skip tensor: fold + the aliased first one in
       // a single store (no staging buffer, no axpy); the tensor is finished
@@ -2568,8 +2577,9 @@ struct ConvBwd {
       if (!add && bs) bw.drop_bsum(rin);
       const bool whole = add || (own && !bw.gwritten[rin] && gather_bwd_mask_ok(fg) && !s3_opt_has(S3O_NO_PLAIN_FOLD16));
       void* side = (whole && fold_side16_ok(pl, o, rin)) ? pl->dpre16 : nullptr;
-      const int rc = add ? launch_gather_bwd_add(ctx, fg, pl->dxp, out, bw.take_alias(rin), bs, side, frame16)
-                         : launch_gather_bwd(ctx, fg, pl->dxp, out, side, frame16);
+      job.side16 = (unsigned short*)side;
+      if (add) { job.mode = FoldJob::ADD; job.aux = bw.take_alias(rin); job.bsum = bs; }
+      const int rc = launch_fold(ctx, fg, job);
       if (!rc && side) bw.claim_dpre16(rin, false);
       return rc;
     }
@@ -2586,9 +2596,12 @@ struct ConvBwd {
                        (po.wgrad == Wgrad::BF16_2D && po.cg.s[0] == 1 && !s3_opt_has(S3O_NO_TRAIN2D_BF16))) &&
                       po.io.in_bf16 && po.d.res < 0 && (po.cg.Cout & 3) == 0 &&
                       (!bw.need_wgrad || po.d.b < 0 || bs != nullptr) && pl->precision == S3_PREC_BF16;
-    const int rc = launch_gather_bwd_masked(ctx, fg, pl->dxp, to16 ? (float*)pl->dpre16 : out, tptr(pl, d.in0),
-                                            pl->t[rin].dtype, po.cg.act == S3_ACT_LEAKY ? po.cg.alpha : 0.f, bs,
-                                            to16 ? 1 : 0, frame16);
+    job.mode = FoldJob::MASKED;
+    job.aux = tptr(pl, d.in0); job.aux_bf16 = pl->t[rin].dtype != 0;
+    job.slope = po.cg.act == S3_ACT_LEAKY ? po.cg.alpha : 0.f;
+    job.bsum = bs;
+    if (to16) { job.din = (float*)pl->dpre16; job.out_bf16 = true; }
+    const int rc = launch_fold(ctx, fg, job);
     if (rc) return rc;
     bw.premasked[rin] = 1;
     if (to16) bw.claim_dpre16(rin, true);
@@ -2730,7 +2743,7 @@ struct ConvBwd {
       // dXpad over the reflect-padded frame, then fold the border back
       rc = launch_gconv_dgrad(ctx, g, dp.f32, o.gc_wt, pl->dxp, 0, 1, 0, x3);
       if (rc) return rc;
-      return launch_gather_bwd(ctx, frame_fold_geom(g, g.lo), pl->dxp, dst);
+      return fold_plain(ctx, frame_fold_geom(g, g.lo), pl->dxp, dst);
     }
     const bool dy16 = o.use16 && dp.bf16 != nullptr;
     return launch_gconv_dgrad(ctx, g, dy16 ? (const float*)dp.bf16 : dp.f32, o.gc_wt, dst, 0, 0, dy16 ? 1 : 0, x3);
@@ -2763,7 +2776,7 @@ struct ConvBwd {
     // dXpad over the padded frame (zero boundary), then fold the border back
     rc = launch_conv_fewpos_dgrad(ctx, conv_fewpos_frame_geom(g), dp.f32, o.fp_wt, pl->dxp, pl->fp_partial, pl->fp_partial_bytes);
     if (rc) return rc;
-    return launch_gather_bwd(ctx, frame_fold_geom(g, g.lo), pl->dxp, dst);
+    return fold_plain(ctx, frame_fold_geom(g, g.lo), pl->dxp, dst);
   }
 
   int dgrad(float* dst) {
@@ -2815,7 +2828,7 @@ static int backward_op(s3_plan* pl, int i, const float* dy) {
     } break;
     case S3_OP_REPEAT_T: case S3_OP_D2S: case S3_OP_PAD: case S3_OP_CROP:
     case S3_OP_ROLL_T: case S3_OP_DILATE:
-      if (want_dx) rc = launch_gather_bwd(ctx, o.gg, dy, dst);
+      if (want_dx) rc = fold_plain(ctx, o.gg, dy, dst);
       break;
     case S3_OP_CONCAT:
       if (want_dx) {

@@ -1,4 +1,5 @@
-"""The training step's support kernels (sup3r_amd/csrc/kernels_misc.hip) at the
+"""The training step's support kernels (sup3r_amd/csrc/kernels_fold.hip,
+kernels_pointwise.hip, kernels_reduce.hip, kernels_optim.hip, kernels_loss_content.hip) at the
 edges of their variants, each against the float64 restatement of the same
 operation (tests/support_ref.py, pinned on the CPU by
 tests/test_support_ref_cpu.py).
@@ -135,12 +136,12 @@ def _gran(a):
     raise AssertionError('values are not multiples of 2^-16')
 
 
-def _reference(spec, nd, weights, x, d_out, exo=None, backwards=1):
+def _reference(spec, nd, weights, x, d_out, exo=None, backwards=1, net=None):
     """float64 reference + the proof that fp32 sums of these terms are exact
     in any order: per conv, sum |dPre| per channel (the bias gradient) and
     max |x| times it (a bound on every weight-gradient sum), counted in units
     of the operands' granularity, stay below 2^24"""
-    ref = R.RefNet(_clean(spec), nd)
+    ref = net or R.RefNet(_clean(spec), nd)     # (net: the caller looks at its tape afterwards)
     ref.set_weights(weights)
     y = ref.forward(x, exo)
     dx = ref.backward(d_out)
@@ -181,7 +182,7 @@ def _assert_exact(got, ref, what, scale=1.0):
 
 
 def _bias_kernel(c, n_pos):
-    """the kernel launch_bias_grad picks (kernels_misc.hip) for a 16-B aligned dPre"""
+    """the kernel launch_bias_grad picks (kernels_reduce.hip) for a 16-B aligned dPre"""
     if c > 256:
         return 'bias_cols_split' if n_pos >= 256 else 'bias_cols'
     return 'bias_stage1_v4' if c % 4 == 0 else 'bias_stage1'
@@ -592,6 +593,65 @@ def test_bf16_frame_fold(trunk_bf16, name, opts, expect, n_persist):
         assert used['bias_partial_ride'] == 2 and used['bias_partial'] == 0 and used['bias_partial_flush'] == 0, used
         assert used['bias_stage1_v4'] == 1, used
     _assert_exact(got[:3], ref, name)
+
+
+# ... and the ADD form on a bf16 frame (fold16x8, MASK 3): s = conv0(x);
+# y = conv3(conv2(act(conv1(s))) + s).  conv 3's fp32 frame is folded plainly
+# onto the sum (with the bf16 copy conv 2 reads), which is also s's first
+# contribution; conv 2's bf16 frame is folded with conv 1's mask; conv 1's bf16
+# frame is folded and ADDED to that first contribution in the same store, with
+# the bf16 copy of the result (dPre of conv 0) unless NO_FOLD16 takes it away.
+# With d_out in [-1, 1] every gradient the plan stores is a multiple of 0.25
+# of at most 8 bits (checked on the reference, below).
+def _bf16_exact(a):
+    a32 = np.asarray(a, np.float32)
+    return bool((a32 == a).all() and ((np.ascontiguousarray(a32).view(np.uint32) & 0xFFFF) == 0).all())
+
+
+@pytest.fixture(scope='module')
+def skip_bf16():
+    spec = _trunk(4, [None, 0.25, None, None], skip=(1, 2), kind='perm')
+    rng = np.random.default_rng(35)
+    w = _weights(spec, 64, rng, 3)
+    x = _data(BF16_SHAPE, rng)
+    d_out = _data(BF16_SHAPE, rng, -1, 1)
+    net = R.RefNet(_clean(spec), 3)
+    ref = _reference(spec, 3, w, x, d_out, net=net)
+    # what the bf16 plan stores — every conv's input (the activations, the skip
+    # sum), what the skip add reads (the sum minus s = conv 2's output) and
+    # every conv's dPre — survives the round trip through bf16 unchanged
+    ins = [rec[4] for rec in net._tape if rec[0] == 'conv']
+    stored = ins + [rec[1] for rec in net._tape if rec[0] == 'act'] + [ins[3] - ins[1]] + list(net.dpre)
+    return spec, w, x, d_out, ref, all(_bf16_exact(t) for t in stored)
+
+
+# Counters of a run with the library of the parent commit.  NO_FOLD16 takes the
+# bf16 side copies away and the plan follows: conv 2 then reads an fp32 dPre
+# and leaves an fp32 frame, and so does conv 0; the one bf16 frame left is
+# conv 1's (its dPre is the bf16-only store of the masked fold), and its fold
+# is the ADD — on the 8-wide walk in both variants, with and without the copy.
+_SKIP16 = {
+    # options: (fold counters, launches of the persistent data gradient)
+    'default': ([('fold_pad4', 1), ('fold16x8', 3), ('fold_plain', 2), ('fold_masked', 1), ('fold_add', 1)], 3),
+    'NO_FOLD16': ([('fold_pad4', 3), ('fold16x8', 1), ('fold_plain', 2), ('fold_masked', 1), ('fold_add', 1)], 1),
+}
+
+
+@pytest.mark.parametrize('name', list(_SKIP16))
+def test_bf16_frame_fold_added_to_a_skip_tensor(skip_bf16, name):
+    spec, w, x, d_out, ref, exact = skip_bf16
+    assert exact, 'a tensor the bf16 plan stores is not bf16-exact: assert_array_equal would mean nothing'
+    expect, n_persist = _SKIP16[name]
+    got = _run(spec, BF16_SHAPE, w, x, d_out, precision='bf16',
+               options=dict(BF16_BASE, **({} if name == 'default' else {name: 1})))
+    used = got[3]
+    print('counters:', {k: v for k, v in used.items() if v}, [i['dgrad'] + '/' + i['wgrad'] for i in got[4]])
+    assert used['persist_dgrad'] == n_persist, used
+    _assert_used(used, expect, [FOLD, FOLD_MODE, AXPY])
+    assert used['fold_add'] == 1 and used['fold16x8'] >= 1, used
+    # (two bias gradients ride along the sums a fold left, two are launch_bias_grad's)
+    assert used['bias_partial_ride'] == 2 and used['bias_stage1_v4'] == 2, used
+    _assert_exact(got[:3], ref, 'skip add on a bf16 frame, ' + name)
 
 
 # ===================================================================== D

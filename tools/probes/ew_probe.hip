@@ -1,6 +1,8 @@
 // Stand-alone timing of the elementwise backward passes (frame fold, mask
 // pass, bias gradient) at the C2 trunk geometry on rotating cold buffers.
-#include "../../sup3r_amd/csrc/kernels_misc.hip"
+#include "../../sup3r_amd/csrc/kernels_fold.hip"
+#include "../../sup3r_amd/csrc/kernels_pointwise.hip"
+#include "../../sup3r_amd/csrc/kernels_reduce.hip"
 #include <vector>
 int main() {
   s3_ctx ctx; hipStreamCreate(&ctx.stream);
@@ -24,9 +26,11 @@ int main() {
       hipEventRecord(e0, ctx.stream);
       for (int i = 0; i < NB; ++i) {
         int rc = 0;
-        if (kind == 0) rc = launch_gather_bwd(&ctx, fg, fr[i], out[i]);
-        if (kind == 1) rc = launch_gather_bwd_masked(&ctx, fg, fr[i], out[i], in[i], 1, 0.2f);
-        if (kind == 2) rc = launch_gather_bwd_add(&ctx, fg, fr[i], out[i], in[i]);
+        FoldJob job;
+        job.frame = fr[i]; job.din = out[i]; job.aux = in[i];
+        if (kind == 1) { job.mode = FoldJob::MASKED; job.aux_bf16 = true; job.slope = 0.2f; }
+        if (kind == 2) job.mode = FoldJob::ADD;
+        if (kind <= 2) rc = launch_fold(&ctx, fg, job);
         if (kind == 3) rc = launch_conv_epilogue_bwd(&ctx, cg, in[i], in[(i + 1) % NB], out[i], 0);
         if (kind == 4) rc = launch_bias_grad(&ctx, in[i], (int64_t)n / 64, 64, db, 0);
         if (kind == 5) rc = launch_axpy(&ctx, in[i], out[i], n);
