@@ -431,8 +431,11 @@ int s3_time_mean(s3_ctx* ctx, float* full, int64_t outer, int t, int c, int t0, 
 /* SpatialFftLoss / SpatiotemporalFftLoss (loss_metrics.py:395-485): separable
  * direct DFT, one call per axis over a contiguous (outer, L, inner) view,
  * unnormalised; sign < 0 = forward (tf.signal.fft2d / fft3d), > 0 = adjoint;
- * in_im may be NULL (real input).  s3_specmap: backward == 0 writes out0 =
- * log(1 + w |X|) with w = k1^2 k2^2 (kt^2 if mode3d) over (n, s1, s2, t, c);
+ * in_im may be NULL (real input).  A workgroup keeps 32 columns and the
+ * twiddles in LDS (264 L bytes): S3_EINVAL for an axis longer than the
+ * device's LDS per workgroup / 264 (620 at the MI355X's 160 KiB).
+ * s3_specmap: backward == 0 writes out0 = log(1 + w |X|) with w = k1^2 k2^2
+ * (kt^2 if mode3d) over (n, s1, s2, t, c);
  * backward != 0 writes (out0, out1) = g_y * w / (1 + w |X|) * X / |X|. */
 int s3_dft_axis(s3_ctx* ctx, const float* in_re, const float* in_im, float* out_re,
                 float* out_im, int64_t outer, int L, int64_t inner, int sign);

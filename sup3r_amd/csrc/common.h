@@ -144,6 +144,7 @@ struct s3_ctx {
   float* scratch = nullptr;  // small device scratch (reductions)
   size_t scratch_bytes = 0;
   int num_cu = 256;
+  size_t lds_max = 64 * 1024;        // LDS a workgroup may declare (device property, s3_ctx_create)
   int64_t stat[S3_STAT_COUNT] = {};   // S3_STAT_* launch counters
   S3Options opt;                     // defaults of the plans created from this context
   hipStream_t comm_stream = nullptr; // bucketed gradient all-reduce under the backward pass

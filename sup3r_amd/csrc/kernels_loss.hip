@@ -450,8 +450,10 @@ extern "C" int s3_loss_mmd(s3_ctx* ctx, const float* a, int c_a, const float* b,
 // SpatialFftLoss / SpatiotemporalFftLoss (loss_metrics.py:395-485): MAE between
 // log(1 + w |FFT(x)|) of generated and true fields, w = product of the squared
 // (un-wrapped) frequency indices.  The transform is a separable direct DFT —
-// one pass per axis over a (outer, L, inner) view, L <= 512 here (80, 288):
-// a workgroup holds a panel of columns and the L twiddles in LDS.  Unnormalised,
+// one pass per axis over a (outer, L, inner) view, L = 80, 288 here: a
+// workgroup holds a panel of 32 columns and the L twiddles in LDS, 264 L bytes,
+// so the longest axis is the device's LDS per workgroup / 264 (620 at 160 KiB);
+// a longer one is S3_EINVAL.  Unnormalised,
 // sign = -1 forward (tf.signal.fft2d / fft3d), +1 for the adjoint.
 namespace {
 
@@ -543,8 +545,13 @@ __global__ void specmap_bwd_kernel(const float* __restrict__ re, const float* __
 extern "C" int s3_dft_axis(s3_ctx* ctx, const float* in_re, const float* in_im, float* out_re,
                            float* out_im, int64_t outer, int L, int64_t inner, int sign) {
   if (!ctx || L < 1 || outer < 1 || inner < 1) return S3_EINVAL;
-  if (L > 1024) S3_FAIL(ctx, S3_EINVAL, "dft_axis: axis longer than 1024");
+  // a workgroup holds its panel and the twiddles in LDS: what the device cannot
+  // hold is an argument error here, not a HIP error at the launch
   const size_t lds = ((size_t)2 * L * DFT_COLS + 2 * L) * sizeof(float);
+  if (lds > ctx->lds_max)
+    S3_FAIL(ctx, S3_EINVAL, "dft_axis: axis of " + std::to_string(L) + " needs " + std::to_string(lds) +
+                                " B of LDS per workgroup, the device has " + std::to_string(ctx->lds_max) +
+                                " (longest axis " + std::to_string(ctx->lds_max / (sizeof(float) * (2 * DFT_COLS + 2))) + ")");
   const int64_t ncol = outer * inner;
   const void* kern = reinterpret_cast<const void*>(dft_axis_kernel);
   if (lds > 64 * 1024)

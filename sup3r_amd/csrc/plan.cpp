@@ -334,6 +334,7 @@ extern "C" int s3_ctx_create(int device_id, void* stream, int create_stream,
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) {
     ctx->num_cu = prop.multiProcessorCount;
+    ctx->lds_max = prop.sharedMemPerBlock;
     // The library is compiled for gfx950 only and its persistent kernels are sized
     // for that part's 160 KB of LDS per workgroup (up to 163,072 B): say so here,
     // once, instead of failing at some kernel's first launch on anything else.
