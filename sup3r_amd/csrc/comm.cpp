@@ -10,11 +10,7 @@
 #include <cstring>
 #include <thread>
 
-#include "common.h"
-
-struct s3_params_view {  // layout prefix of s3_params (plan.cpp)
-  s3_ctx* ctx;
-};
+#include "plan_internal.h"
 
 namespace {
 typedef struct { char internal[128]; } ncclUniqueId_t;
@@ -107,7 +103,7 @@ extern "C" int s3_allreduce_sum(s3_ctx* ctx, float* buf, int64_t n) {
 
 // ---- bucketed all-reduce overlapped with the backward pass ----------------
 // s3_plan_backward hands over the finished tail of the gradient buffer bucket
-// by bucket (plan.cpp); each bucket is reduced on a second stream behind an
+// by bucket (plan_backward.cpp); each bucket is reduced on a second stream behind an
 // event on the compute stream, so RCCL's xGMI traffic runs under the
 // remaining weight / data gradient kernels.  Collectives are issued in the
 // same order on every rank (the op order of the plan).
@@ -245,7 +241,7 @@ extern "C" int s3_comm_info(s3_ctx* ctx, int* n_ranks, int* rank) {
 
 extern "C" int s3_params_broadcast(s3_params* p, int which, int root) {
   if (!p || which < 0 || which > 3) return S3_EINVAL;
-  s3_ctx* ctx = reinterpret_cast<s3_params_view*>(p)->ctx;
+  s3_ctx* ctx = p->ctx;
   int rc = s3_broadcast(ctx, (float*)s3_params_dptr(p, which, -1), s3_params_total(p), root);
   if (rc == S3_OK && which == S3_BUF_W) (void)s3_params_touch(p);
   return rc;
@@ -253,7 +249,7 @@ extern "C" int s3_params_broadcast(s3_params* p, int which, int root) {
 
 extern "C" int s3_params_allreduce_grads(s3_params* p) {
   if (!p) return S3_EINVAL;
-  s3_ctx* ctx = reinterpret_cast<s3_params_view*>(p)->ctx;
+  s3_ctx* ctx = p->ctx;
   int n_buckets = 0;
   const int armed = s3_params_take_armed(p, &n_buckets);
   if (armed == 1) return comm_join(ctx);       // reduced bucket by bucket under the backward pass

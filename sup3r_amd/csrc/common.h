@@ -153,7 +153,7 @@ struct s3_ctx {
   int64_t comm_issued = 0;           // collectives enqueued since the last completed s3_comm_wait
   // option WGRAD_SIDE_STREAM (an experiment that lost, kept for the A/B): weight
   // gradients of launch-bound backward passes beside the data-gradient chain
-  // (plan.cpp: wg_fork / wg_join; joins every s3_plan_backward)
+  // (plan_backward.cpp: wg_fork / wg_join; joins every s3_plan_backward)
   hipStream_t wg_stream = nullptr;
   hipEvent_t wg_ev[2] = {nullptr, nullptr};    // [0] compute -> side, [1] side -> compute
   bool wg_forked = false;

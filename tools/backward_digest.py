@@ -24,7 +24,7 @@ sys.path.insert(0, ROOT)
 FORCE = {'HALO32_MIN_TILES': 1, 'FEWCH_HALO_MIN_TILES': 1, 'DGRAD_S2_MIN_TILES': 1,
          'PERSIST_DGRAD_MIN_TILES': 1, 'HALO_S2_MIN_TILES': 1}
 ALONE = ('NO_MASK_FUSE', 'NO_BIAS_FUSE', 'NO_FOLD16', 'NO_PLAIN_FOLD16', 'NO_DPRE16', 'NO_DPRE16_ONLY_MASK')
-# every Wgrad / Dgrad of csrc/plan.cpp; s3_plan_op_info merges some of them:
+# every Wgrad / Dgrad of csrc/plan_internal.h; s3_plan_op_info merges some of them:
 # told apart below by the precision (x3), the op's padding (chunked) and the
 # fewpos_mfma / forward-kernel fields (approximate for fewpos and gen)
 WGRADS = ('direct', 'fewpos_mfma', 'fewpos', 'tail', 'c2', 'bf16_trunk', 'f32_trunk', 'bf16_gen', 'bf16_2d', 'f32_gen')
