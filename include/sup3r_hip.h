@@ -688,6 +688,64 @@ int s3_sample_gather(s3_ctx* ctx, const float* data, int64_t S1, int64_t S2, int
                      const int* origins_host, int n, int s1, int s2, int t,
                      const int* channel_host, int c_out, float* out);
 
+/* ---- DualSamplerCC: daylight window and nearest-neighbour fill ---------------
+ * replaces what DualSamplerCC.__next__ (sup3r/preprocessing/samplers/cc.py:
+ * 185-203) does to a batch on the host after cutting it: nsrdb_reduce_daily_data
+ * (samplers/utilities.py:258-297) and nn_fill_array (sup3r/utilities/
+ * utilities.py:55-75, scipy.ndimage.distance_transform_edt with indices).
+ *
+ * status: S3_CC_STATUS_WORDS 32-bit words on the device, read by nobody on the
+ * host unless asked for:
+ *   [S3_CC_NIGHT_MASK] bit k: the channel is NaN somewhere at hour k of the
+ *                      24-hour windows;
+ *   [S3_CC_START_RAW]  first hour kept as the reference computes it: the first
+ *                      daylight hour - ceil((t - daylight hours) / 2);
+ *   [S3_CC_START]      the hour the gather started at;
+ *   [S3_CC_FILLED]     NaNs s3_nn_fill found in its channel (every one of them
+ *                      is filled unless the channel holds nothing else).
+ *
+ * s3_cc_night_mask: zeroes the status words (asynchronously), then ORs the
+ * mask of the n 24-hour windows data[i0 + i, j0 + j, k0 .. k0 + 24, channel]
+ * (i < s1, j < s2; origins as for s3_sample_gather) into the first.
+ *
+ * s3_cc_window_gather: s3_sample_gather, but the origins are those of the
+ * 24-hour windows and
+ *   out[m, i, j, k, q] = data[i0[m] + i, j0[m] + j, k0[m] + start + k, channel[q]]
+ * for t < 24 hours, start computed on the device from status[S3_CC_NIGHT_MASK]
+ * and recorded.  Two deviations from the reference: start is clamped into
+ * [0, 24 - t] (the reference's slice(start, start + t) of 24 steps comes out
+ * short or empty when start is negative or past 24 - t), and 24 hours of night
+ * give the centred window start = (24 - t) / 2 (the reference warns and
+ * returns all 24 hours).
+ *
+ * s3_nn_fill: in place, on channel `channel` of the contiguous fp32 block x
+ * (n, s1, s2, t, C): every element whose bits are a NaN receives the bits of
+ * the non-NaN element of that channel that minimises (dn^2 + di^2 + dj^2 +
+ * dk^2, column-major index m + n (i + s1 (j + s2 k))) — the element scipy
+ * picks, ties included.  Nothing else is written: other channels (their NaNs
+ * too), -0.0, infinities and denormals keep their bits; a channel without NaN
+ * or with nothing but NaN is left as it is (the kernels behind the first see
+ * the count on the device and return).  work: 8 bytes per element of the
+ * channel (n * s1 * s2 * t), 8-byte aligned; count: one status word, zeroed
+ * here.  S3_EINVAL: an extent above S3_NN_FILL_MAX_AXIS (lines are staged in
+ * LDS whole; squared distances stay far below 2^32), 2^31 or more elements of
+ * the channel.
+ *
+ * All three are asynchronous on the context's stream; nothing is uploaded. */
+#define S3_CC_STATUS_WORDS 4
+#define S3_CC_NIGHT_MASK 0
+#define S3_CC_START_RAW 1
+#define S3_CC_START 2
+#define S3_CC_FILLED 3
+#define S3_NN_FILL_MAX_AXIS 2048
+int s3_cc_night_mask(s3_ctx* ctx, const float* data, int64_t S1, int64_t S2, int64_t T, int C,
+                     const int* origins_host, int n, int s1, int s2, int channel, int* status);
+int s3_cc_window_gather(s3_ctx* ctx, const float* data, int64_t S1, int64_t S2, int64_t T, int C,
+                        const int* origins_host, int n, int s1, int s2, int t,
+                        const int* channel_host, int c_out, int* status, float* out);
+int s3_nn_fill(s3_ctx* ctx, float* x, int n, int s1, int s2, int t, int C, int channel,
+               void* work, int* count);
+
 /* ---- bias correction of forward-pass chunks on the device ------------------
  * replaces the host numpy / rex of ForwardPassStrategy.prep_chunk_data
  * (sup3r/pipeline/strategy.py:502-517 -> bias_correct_features ->

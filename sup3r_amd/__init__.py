@@ -30,6 +30,8 @@ from . import batch_queue_conditional as _cond  # noqa: E402
 from .batch_queue_conditional import *  # noqa: E402,F401,F403
 from . import samplers as _samplers  # noqa: E402
 from .samplers import *  # noqa: E402,F401,F403
+from . import samplers_cc as _samplers_cc  # noqa: E402
+from .samplers_cc import *  # noqa: E402,F401,F403
 from . import batch_queue_dc as _dc  # noqa: E402
 from .batch_queue_dc import *  # noqa: E402,F401,F403
 from . import batch_queue_dual as _dual  # noqa: E402
@@ -39,4 +41,4 @@ __all__ = ['Sup3rGan', 'Sup3rCondMom', 'Sup3rGanDC', 'SolarCC', 'Sup3rGanWithObs
            'MultiStepSurfaceMetGan', 'SolarMultiStepGan', 'LinearInterp', 'SurfaceSpatialMetModel', 'ForwardPass', 'ChunkPathOptions',
            'ChunkSlicer', 'BiasParams', 'DeviceBiasCorrection', 'global_linear_bc', 'local_linear_bc',
            'monthly_local_linear_bc', 'local_qdm_bc', 'local_presrat_bc', 'DeviceBatchQueue', 'DeviceBatchHandler', 'DsetTuple',
-           *_cond.__all__, *_samplers.__all__, *_dc.__all__, *_dual.__all__, '__version__']
+           *_cond.__all__, *_samplers.__all__, *_samplers_cc.__all__, *_dc.__all__, *_dual.__all__, '__version__']

@@ -43,7 +43,8 @@ EXPORTS = [
     's3_specmap',
     's3_copy_channels', 's3_affine_channels', 's3_fill', 's3_copy_block',
     's3_coarsen', 's3_gaussian_smooth', 's3_condmom_target', 's3_bias_correct', 's3_chunk_stats',
-    's3_sample_gather',
+    's3_sample_gather', 's3_cc_night_mask', 's3_cc_window_gather',
+    's3_nn_fill',
     's3_st_interp', 's3_resize2d', 's3_surface_downscale',
     's3_chunk_epilogue', 's3_chunk_time_last', 's3_chunk_time_first',
     's3_step_handover', 's3_broadcast_axis', 's3_branch_join',
@@ -243,6 +244,12 @@ def lib():
         's3_sample_gather': (i32, [vp, vp, i64, i64, i64, i32, C.POINTER(i32),
                                    i32, i32, i32, i32, C.POINTER(i32), i32,
                                    vp]),
+        's3_cc_night_mask': (i32, [vp, vp, i64, i64, i64, i32, C.POINTER(i32),
+                                   i32, i32, i32, i32, vp]),
+        's3_cc_window_gather': (i32, [vp, vp, i64, i64, i64, i32,
+                                      C.POINTER(i32), i32, i32, i32, i32,
+                                      C.POINTER(i32), i32, vp, vp]),
+        's3_nn_fill': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         's3_bias_correct': (i32, [vp, vp, i32, i32, i32, i32, i32,
                                   C.POINTER(BiasChannel), i32, i32,
                                   C.POINTER(i32), vp, vp, vp,
@@ -323,6 +330,10 @@ TC_METHODS = {'subsample': 0, 'average': 1, 'total': 2, 'max': 3, 'min': 4}
 CM_SUBFILTER, CM_LINEAR, CM_MOM1, CM_SQUARE = 1, 2, 4, 8
 # s3_sample_gather: samples per launch, channels kept (include/sup3r_hip.h)
 SAMPLE_MAX_ORIGINS, SAMPLE_MAX_CHANNELS = 64, 32
+# DualSamplerCC's status words and the fill's largest extent (include/sup3r_hip.h)
+CC_STATUS_WORDS = 4
+CC_NIGHT_MASK, CC_START_RAW, CC_START, CC_FILLED = 0, 1, 2, 3
+NN_FILL_MAX_AXIS = 2048
 # s3_bias_correct: limits, channel kinds, flags (include/sup3r_hip.h)
 BC_MAX_CHANNELS, BC_MAX_CHUNKS = 16, 32
 BC_NONE, BC_LINEAR, BC_QDM = 0, 1, 2

@@ -93,8 +93,17 @@ class DeviceDualBatchHandler(DeviceBatchHandler, DeviceDualBatchQueue):
     VAL_QUEUE = DeviceDualBatchQueue
 
 
+class DeviceBatchHandlerCC(DeviceDualBatchHandler):
+    """``BatchHandlerCC`` (batch_handlers/factory.py:319-321:
+    ``BatchHandlerFactory(DualBatchQueue, DualSamplerCC)``): the dual queues
+    over :class:`~sup3r_amd.samplers_cc.DeviceDualSamplerCC` samplers, which
+    hand out daily low-res / hourly high-res batches with the clearsky ratio
+    reduced to daylight and filled — what ``SolarCC`` trains on."""
+
+
 # the reference's names
 DualBatchQueue, DualBatchHandler = DeviceDualBatchQueue, DeviceDualBatchHandler
+BatchHandlerCC = DeviceBatchHandlerCC
 
 __all__ = ['DeviceDualBatchQueue', 'DeviceDualBatchHandler', 'DualBatchQueue',
-           'DualBatchHandler']
+           'DualBatchHandler', 'DeviceBatchHandlerCC', 'BatchHandlerCC']

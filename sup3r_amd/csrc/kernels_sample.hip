@@ -23,6 +23,9 @@
 //     one piece however the loads scatter; the position is decomposed once per
 //     lane and carried from element to element.
 // A pure copy: no arithmetic touches a value, NaN payloads arrive as they are.
+// s3_cc_window_gather is the second kernel with one more step: its boxes are
+// 24-hour windows and the t hours it keeps start where the night mask that
+// s3_cc_night_mask (kernels_cc.hip) left on the device says.
 #include "common.h"
 
 namespace {
@@ -149,12 +152,37 @@ __device__ __forceinline__ void decompose(const SgGeom& g, uint32_t e, uint32_t&
   m = g.dS1(mi); i = mi - m * g.s1;
 }
 
-template <bool VEC>
+// first hour kept of a 24-hour window whose night hours are the set bits of
+// `mask` (nsrdb_reduce_daily_data, samplers/utilities.py:281-297): the first
+// daylight hour minus half of what t exceeds the daylight hours by, the half
+// rounded towards +inf; `raw` is that start as the reference computes it.
+// Deviations (include/sup3r_hip.h): the start is clamped into [0, 24 - t], and
+// 24 hours of night give the centred window.
+__device__ __forceinline__ int window_start(unsigned mask, int t, int& raw) {
+  const unsigned day = ~mask & 0xFFFFFFu;
+  if (day == 0) return raw = (24 - t) / 2;
+  const int pad = t - __popc(day);
+  const int half = pad >= 0 ? (pad + 1) / 2 : -((-pad) / 2);
+  raw = (__ffs((int)day) - 1) - half;
+  return raw < 0 ? 0 : raw > 24 - t ? 24 - t : raw;
+}
+
+// WIN: the boxes are 24-hour windows and the copy starts window_start() hours
+// into them, computed by every workgroup from the night mask in status[0]
+template <bool VEC, bool WIN>
 __global__ void __launch_bounds__(kBlk)
-sample_gather_short_kernel(SgGeom g, const float* __restrict__ data, float* __restrict__ out) {
+sample_gather_short_kernel(SgGeom g, const float* __restrict__ data, float* __restrict__ out,
+                           int* __restrict__ status) {
   __shared__ int s_ch[kMaxC];
+  __shared__ int s_start;
   if (threadIdx.x < kMaxC) s_ch[threadIdx.x] = g.ch[threadIdx.x];
+  if (WIN && threadIdx.x == 0) {
+    int raw;
+    s_start = window_start((unsigned)status[S3_CC_NIGHT_MASK], (int)g.t, raw);
+    if (blockIdx.x == 0) { status[S3_CC_START_RAW] = raw; status[S3_CC_START] = s_start; }
+  }
   __syncthreads();
+  if (WIN) data += (int64_t)s_start * g.C;
   const uint32_t gid = blockIdx.x * kBlk + threadIdx.x, stride = gridDim.x * kBlk;
   uint32_t m, i, j, k, q;
   if (VEC) {
@@ -198,32 +226,37 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
 
-extern "C" int s3_sample_gather(s3_ctx* ctx, const float* data, int64_t S1, int64_t S2, int64_t T,
-                                int C, const int* origins_host, int n, int s1, int s2, int t,
-                                const int* channel_host, int c_out, float* out) {
-  if (!ctx) return S3_EINVAL;
+// status == nullptr: s3_sample_gather.  Otherwise s3_cc_window_gather: the
+// boxes that must fit the cube are the 24-hour windows
+static int gather_impl(s3_ctx* ctx, const char* who, const float* data, int64_t S1, int64_t S2, int64_t T,
+                       int C, const int* origins_host, int n, int s1, int s2, int t,
+                       const int* channel_host, int c_out, int* status, float* out) {
+  const bool win = status != nullptr;
+  const int t_box = win ? 24 : t;
   if (!data || !out || !origins_host || !channel_host)
-    S3_FAIL(ctx, S3_EINVAL, "sample_gather: data, out, the origins and the channel map are needed");
-  if (S1 < 1 || S2 < 1 || T < 1 || C < 1) S3_FAIL(ctx, S3_EINVAL, "sample_gather: empty cube");
-  if (n < 1 || s1 < 1 || s2 < 1 || t < 1) S3_FAIL(ctx, S3_EINVAL, "sample_gather: empty batch");
-  if (c_out < 1 || c_out > kMaxC) S3_FAIL(ctx, S3_EINVAL, "sample_gather: 1 .. 32 channels are kept");
-  if (s1 > S1 || s2 > S2 || t > T) S3_FAIL(ctx, S3_EINVAL, "sample_gather: the box is larger than the cube");
+    S3_FAIL(ctx, S3_EINVAL, std::string(who) + ": data, out, the origins and the channel map are needed");
+  if (S1 < 1 || S2 < 1 || T < 1 || C < 1) S3_FAIL(ctx, S3_EINVAL, std::string(who) + ": empty cube");
+  if (n < 1 || s1 < 1 || s2 < 1 || t < 1) S3_FAIL(ctx, S3_EINVAL, std::string(who) + ": empty batch");
+  if (c_out < 1 || c_out > kMaxC) S3_FAIL(ctx, S3_EINVAL, std::string(who) + ": 1 .. 32 channels are kept");
+  if (win && t >= 24)
+    S3_FAIL(ctx, S3_EINVAL, std::string(who) + ": 1 .. 23 hours are kept of a 24-hour window");
+  if (s1 > S1 || s2 > S2 || t_box > T) S3_FAIL(ctx, S3_EINVAL, std::string(who) + ": the box is larger than the cube");
   if (T > INT32_MAX || S1 > INT32_MAX || S2 > INT32_MAX)
-    S3_FAIL(ctx, S3_EINVAL, "sample_gather: 32-bit cube extents (offsets are 64-bit)");
+    S3_FAIL(ctx, S3_EINVAL, std::string(who) + ": 32-bit cube extents (offsets are 64-bit)");
   bool identity = c_out == C;
   for (int q = 0; q < c_out; ++q) {
     if (channel_host[q] < 0 || channel_host[q] >= C)
-      S3_FAIL(ctx, S3_EINVAL, "sample_gather: channel map entry outside the cube's channels");
+      S3_FAIL(ctx, S3_EINVAL, std::string(who) + ": channel map entry outside the cube's channels");
     identity = identity && channel_host[q] == q;
   }
   for (int m = 0; m < n; ++m) {
     const int* o = origins_host + (size_t)m * 3;
-    if (o[0] < 0 || o[1] < 0 || o[2] < 0 || o[0] > S1 - s1 || o[1] > S2 - s2 || o[2] > T - t)
-      S3_FAIL(ctx, S3_EINVAL, "sample_gather: a box leaves the cube");
+    if (o[0] < 0 || o[1] < 0 || o[2] < 0 || o[0] > S1 - s1 || o[1] > S2 - s2 || o[2] > T - t_box)
+      S3_FAIL(ctx, S3_EINVAL, std::string(who) + ": a box leaves the cube");
   }
   const int64_t per_sample = (int64_t)s1 * s2 * t * c_out;
   if (per_sample >= ((int64_t)1 << 31) || per_sample * n >= ((int64_t)1 << 31))
-    S3_FAIL(ctx, S3_EINVAL, "sample_gather: 32-bit element indices of out");
+    S3_FAIL(ctx, S3_EINVAL, std::string(who) + ": 32-bit element indices of out");
   SgGeom g;
   g.S2 = S2; g.TC = T * C;
   g.s1 = s1; g.s2 = s2; g.t = t; g.C = C; g.c_out = c_out;
@@ -231,7 +264,7 @@ extern "C" int s3_sample_gather(s3_ctx* ctx, const float* data, int64_t S1, int6
   g.dRun = FastDiv((uint32_t)t * c_out); g.dCo = FastDiv(c_out);
   g.dS2 = FastDiv(s2); g.dS1 = FastDiv(s1);
   for (int q = 0; q < kMaxC; ++q) g.ch[q] = q < c_out ? channel_host[q] : 0;
-  const bool long_runs = (int64_t)t * C >= kLongRun && C <= kLongMaxC;
+  const bool long_runs = !win && (int64_t)t * C >= kLongRun && C <= kLongMaxC;
   g.tseg = long_runs ? kSeg / C : 1;
   for (int m0 = 0; m0 < n; m0 += kMaxN) {
     const int nl = n - m0 < kMaxN ? n - m0 : kMaxN;
@@ -250,14 +283,28 @@ extern "C" int s3_sample_gather(s3_ctx* ctx, const float* data, int64_t S1, int6
       int64_t grid = (items + kBlk - 1) / kBlk;
       const int64_t cap = (int64_t)ctx->num_cu * 8;
       if (grid > cap) grid = cap;
-      if (vec)
-        hipLaunchKernelGGL(sample_gather_short_kernel<true>, dim3((unsigned)grid), dim3(kBlk), 0,
-                           ctx->stream, g, data, dst);
-      else
-        hipLaunchKernelGGL(sample_gather_short_kernel<false>, dim3((unsigned)grid), dim3(kBlk), 0,
-                           ctx->stream, g, data, dst);
+      auto kernel = win ? (vec ? sample_gather_short_kernel<true, true> : sample_gather_short_kernel<false, true>)
+                        : (vec ? sample_gather_short_kernel<true, false> : sample_gather_short_kernel<false, false>);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kBlk), 0, ctx->stream, g, data, dst, status);
     }
     S3_HIP(ctx, hipGetLastError());
   }
   return S3_OK;
+}
+
+extern "C" int s3_sample_gather(s3_ctx* ctx, const float* data, int64_t S1, int64_t S2, int64_t T,
+                                int C, const int* origins_host, int n, int s1, int s2, int t,
+                                const int* channel_host, int c_out, float* out) {
+  if (!ctx) return S3_EINVAL;
+  return gather_impl(ctx, "sample_gather", data, S1, S2, T, C, origins_host, n, s1, s2, t, channel_host, c_out,
+                     nullptr, out);
+}
+
+extern "C" int s3_cc_window_gather(s3_ctx* ctx, const float* data, int64_t S1, int64_t S2, int64_t T,
+                                   int C, const int* origins_host, int n, int s1, int s2, int t,
+                                   const int* channel_host, int c_out, int* status, float* out) {
+  if (!ctx) return S3_EINVAL;
+  if (!status) S3_FAIL(ctx, S3_EINVAL, "s3_cc_window_gather: the status words are needed");
+  return gather_impl(ctx, "s3_cc_window_gather", data, S1, S2, T, C, origins_host, n, s1, s2, t, channel_host,
+                     c_out, status, out);
 }

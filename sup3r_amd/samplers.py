@@ -31,8 +31,9 @@ logic runs without a GPU — the counterpart of ``DeviceBatchQueue(transform=)``
 Multi-GPU: every rank holds its own copy of the cube (the samplers are built
 per process, on ``Device.get()`` of that rank) and draws with its own seed.
 
-Not here: ``DualSamplerCC`` (daylight reduction, ``nn_fill`` of hourly data)
-and reading containers from files.
+``DualSamplerCC`` (daily / hourly pairs, daylight reduction and ``nn_fill`` of
+the clearsky ratio) is in samplers_cc.py.  Not here: reading containers from
+files.
 """
 import ctypes as C
 import logging
