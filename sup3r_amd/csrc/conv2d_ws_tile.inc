@@ -122,10 +122,10 @@
   // CU, before the straight-line form): read-only 3.8 us per tile (5.5 TB/s),
   // write-only 3.3 us (5.0 TB/s), tap loop 3.0 us, everything 10.4 - 10.7 us —
   // the sum, because of the waits described at the top of this file.
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  WG_BARRIER_LDS();
   WS_COMMIT();
   WS_ECOMMIT();
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  WG_BARRIER_LDS();
 #endif
 
   // ---- epilogue from registers: lane (position column frow, channel
@@ -162,22 +162,22 @@
       const unsigned long long dst = tbase + (unsigned long long)(unsigned)rc * RS + off_h[h];
       if constexpr (RES) {
         const uint4 q4 = rr[m][h];
-        v[0] += ws_lo(q4.x); v[1] += ws_hi(q4.x); v[2] += ws_lo(q4.y); v[3] += ws_hi(q4.y);
-        v[4] += ws_lo(q4.z); v[5] += ws_hi(q4.z); v[6] += ws_lo(q4.w); v[7] += ws_hi(q4.w);
+        v[0] += bf_lo(q4.x); v[1] += bf_hi(q4.x); v[2] += bf_lo(q4.y); v[3] += bf_hi(q4.y);
+        v[4] += bf_lo(q4.z); v[5] += bf_hi(q4.z); v[6] += bf_lo(q4.w); v[7] += bf_hi(q4.w);
       }
       if (res2) {
         // (d2s == 1; the sum of the first skip is rounded to bf16 first, as
         // the separate add of two bf16 tensors saw it)
         uint4 o1;
-        o1.x = ws_pk(v[0], v[1]); o1.y = ws_pk(v[2], v[3]); o1.z = ws_pk(v[4], v[5]); o1.w = ws_pk(v[6], v[7]);
+        o1.x = pk2(v[0], v[1]); o1.y = pk2(v[2], v[3]); o1.z = pk2(v[4], v[5]); o1.w = pk2(v[6], v[7]);
         const uint4 q4 = *reinterpret_cast<const uint4*>(res2 + dst);
-        v[0] = ws_lo(o1.x) + ws_lo(q4.x); v[1] = ws_hi(o1.x) + ws_hi(q4.x);
-        v[2] = ws_lo(o1.y) + ws_lo(q4.y); v[3] = ws_hi(o1.y) + ws_hi(q4.y);
-        v[4] = ws_lo(o1.z) + ws_lo(q4.z); v[5] = ws_hi(o1.z) + ws_hi(q4.z);
-        v[6] = ws_lo(o1.w) + ws_lo(q4.w); v[7] = ws_hi(o1.w) + ws_hi(q4.w);
+        v[0] = bf_lo(o1.x) + bf_lo(q4.x); v[1] = bf_hi(o1.x) + bf_hi(q4.x);
+        v[2] = bf_lo(o1.y) + bf_lo(q4.y); v[3] = bf_hi(o1.y) + bf_hi(q4.y);
+        v[4] = bf_lo(o1.z) + bf_lo(q4.z); v[5] = bf_hi(o1.z) + bf_hi(q4.z);
+        v[6] = bf_lo(o1.w) + bf_lo(q4.w); v[7] = bf_hi(o1.w) + bf_hi(q4.w);
       }
       uint4 o;
-      o.x = ws_pk(v[0], v[1]); o.y = ws_pk(v[2], v[3]); o.z = ws_pk(v[4], v[5]); o.w = ws_pk(v[6], v[7]);
+      o.x = pk2(v[0], v[1]); o.y = pk2(v[2], v[3]); o.z = pk2(v[4], v[5]); o.w = pk2(v[6], v[7]);
       if (row_ok && ch_ok[h]) *reinterpret_cast<uint4*>(y + dst) = o;
     }
   }

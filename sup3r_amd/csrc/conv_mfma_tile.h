@@ -5,14 +5,9 @@
 #pragma once
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int TS2 = 16;
 constexpr int H2 = TS2 + 2;
@@ -21,25 +16,10 @@ constexpr int CT = 64;          // cout tile
 constexpr int F32_ROW = 66;     // halo row stride (dwords), f32 mode
 constexpr int F32_BROW = 80;    // filter row stride (dwords), f32 mode
 
-// two fp32 -> packed bf16x2 (v_cvt_pk_bf16_f32, round-to-nearest-even)
-__device__ inline unsigned pack_bf16(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
-__device__ inline float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ inline float bf_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
-
 __device__ inline unsigned short f2bf(float f) {
   unsigned u = __float_as_uint(f);
   u += 0x7FFFu + ((u >> 16) & 1u);   // round to nearest even
   return (unsigned short)(u >> 16);
-}
-
-__device__ inline float act_f(float v, int act, float alpha) {
-  // one select for every kind (slope 1 = identity, 0 = ReLU, alpha = Leaky):
-  // testing the kind per element compiles to two scalar branches per value
-  const float s = act == S3_ACT_LEAKY ? alpha : (act == S3_ACT_RELU ? 0.f : 1.f);
-  return v > 0.f ? v : s * v;
 }
 
 // KA: taps along logical axis 0 (3, or 1 for the 2-D nets whose axis 0 is the
@@ -251,17 +231,17 @@ __global__ __launch_bounds__(NW * 64) void conv3_mfma_kernel(
               o = va[u];
             } else {
               const uint4 a = va[u], b = vb[IN16 ? 0 : u];
-              o.x = pack_bf16(__uint_as_float(a.x), __uint_as_float(a.y));
-              o.y = pack_bf16(__uint_as_float(a.z), __uint_as_float(a.w));
-              o.z = pack_bf16(__uint_as_float(b.x), __uint_as_float(b.y));
-              o.w = pack_bf16(__uint_as_float(b.z), __uint_as_float(b.w));
+              o.x = pk2(__uint_as_float(a.x), __uint_as_float(a.y));
+              o.y = pk2(__uint_as_float(a.z), __uint_as_float(a.w));
+              o.z = pk2(__uint_as_float(b.x), __uint_as_float(b.y));
+              o.w = pk2(__uint_as_float(b.z), __uint_as_float(b.w));
               if (X3) {
                 // lo = bf16(v - hi): the residue of the first rounding
                 uint4 l;
-                l.x = pack_bf16(__uint_as_float(a.x) - bf_lo(o.x), __uint_as_float(a.y) - bf_hi(o.x));
-                l.y = pack_bf16(__uint_as_float(a.z) - bf_lo(o.y), __uint_as_float(a.w) - bf_hi(o.y));
-                l.z = pack_bf16(__uint_as_float(b.x) - bf_lo(o.z), __uint_as_float(b.y) - bf_hi(o.z));
-                l.w = pack_bf16(__uint_as_float(b.z) - bf_lo(o.w), __uint_as_float(b.w) - bf_hi(o.w));
+                l.x = pk2(__uint_as_float(a.x) - bf_lo(o.x), __uint_as_float(a.y) - bf_hi(o.x));
+                l.y = pk2(__uint_as_float(a.z) - bf_lo(o.y), __uint_as_float(a.w) - bf_hi(o.y));
+                l.z = pk2(__uint_as_float(b.x) - bf_lo(o.z), __uint_as_float(b.y) - bf_hi(o.z));
+                l.w = pk2(__uint_as_float(b.z) - bf_lo(o.w), __uint_as_float(b.w) - bf_hi(o.w));
                 const int slot_lo = (4 + ch) ^ ((hp % H2) & 7);
                 *reinterpret_cast<uint4*>(halo + (size_t)hp * 128 + slot_lo * 16) = l;
               }
@@ -559,8 +539,8 @@ __global__ __launch_bounds__(NW * 64) void conv3_mfma_kernel(
       }
       if (OUT16) {
         uint4 o;
-        o.x = pack_bf16(v[0], v[1]); o.y = pack_bf16(v[2], v[3]);
-        o.z = pack_bf16(v[4 % CPT], v[5 % CPT]); o.w = pack_bf16(v[6 % CPT], v[7 % CPT]);
+        o.x = pk2(v[0], v[1]); o.y = pk2(v[2], v[3]);
+        o.z = pk2(v[4 % CPT], v[5 % CPT]); o.w = pk2(v[6 % CPT], v[7 % CPT]);
         *reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(yv) + dst) = o;
       } else {
         *reinterpret_cast<float4*>(reinterpret_cast<float*>(yv) + dst) =

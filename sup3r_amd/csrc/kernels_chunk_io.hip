@@ -3,6 +3,7 @@
 // the 2-D models' time-first / time-last transposes, the MultiStepGan step
 // hand-over and the device -> host placement of finished chunks.
 #include "kernels_support.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -531,12 +532,11 @@ extern "C" int s3_d2h_window(s3_ctx* ctx, const float* src, float* dst_host, int
 // 16-B stores in flight per lane saturate it, so the copy is a grid of
 // `blocks` workgroups (default 16 of the 256 CUs' worth) writing through the
 // host-mapped pointer; everything else of the chip stays with the forward pass.
-typedef unsigned d2h_u32x4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void d2h_stream_kernel(const d2h_u32x4* __restrict__ src,
-                                                         d2h_u32x4* __restrict__ dst, size_t n16) {
+__global__ __launch_bounds__(256) void d2h_stream_kernel(const u32x4* __restrict__ src,
+                                                         u32x4* __restrict__ dst, size_t n16) {
   const size_t stride = (size_t)gridDim.x * 256 * 4;
   for (size_t i = (size_t)blockIdx.x * 256 * 4 + threadIdx.x; i < n16; i += stride) {
-    d2h_u32x4 v[4];
+    u32x4 v[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       if (i + q * 256 < n16) v[q] = __builtin_nontemporal_load(src + i + q * 256);
@@ -563,7 +563,7 @@ extern "C" int s3_d2h_stream(s3_ctx* ctx, const void* src, void* dst_host, size_
   const size_t need = (n16 + 1023) / 1024;
   if ((size_t)blocks > need) blocks = (int)need;
   hipLaunchKernelGGL(d2h_stream_kernel, dim3(blocks), dim3(256), 0,
-                     stream ? (hipStream_t)stream : ctx->stream, (const d2h_u32x4*)src, (d2h_u32x4*)dptr, n16);
+                     stream ? (hipStream_t)stream : ctx->stream, (const u32x4*)src, (u32x4*)dptr, n16);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }

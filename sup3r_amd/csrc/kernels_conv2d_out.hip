@@ -25,25 +25,13 @@
 // A workgroup of G waves owns a strip of 16 G halo columns (16 G - 2 outputs) of one
 // image and walks a segment of rows; a wave = 16 cells of each halo row; loads run
 // four rows ahead in registers; one barrier per row.
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 obf16x2 __attribute__((ext_vector_type(2)));
-typedef float of32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int OUT_MAX_COUT = 7;
 constexpr int OUT_SLOTS = 4;
 constexpr int OUT_AHEAD = 4;          // halo rows in flight per wave
-
-__device__ inline unsigned out_pk(float a, float b) {
-  of32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, obf16x2));
-}
-__device__ inline float out_lo16(unsigned u) { return __uint_as_float(u << 16); }
-__device__ inline float out_hi16(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
 
 // canonical fp32 w[tap 9][ci 64][co C_out] -> B fragments, one 16 B per lane:
 // image[sel][ks][nf][lane] = 8 bf16: k = ks 32 + (lane >> 4) 8 + e, column nf 16 +
@@ -59,8 +47,8 @@ __global__ void pack_out_kernel(const float* __restrict__ w, unsigned short* __r
     const int tap = col / cout, co = col % cout;
     v = w[((size_t)tap * 64 + k) * cout + co];
   }
-  const unsigned hi = out_pk(v, 0.f) & 0xFFFFu;
-  const unsigned lo = out_pk(v - __uint_as_float(hi << 16), 0.f) & 0xFFFFu;
+  const unsigned hi = pk2(v, 0.f) & 0xFFFFu;
+  const unsigned lo = pk2(v - __uint_as_float(hi << 16), 0.f) & 0xFFFFu;
   out[idx] = (unsigned short)(sel ? lo : hi);
 }
 
@@ -161,8 +149,8 @@ __global__ __launch_bounds__(64 * OUT_WAVES) void conv2d_out_kernel(
           unsigned h[4], l[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            h[e] = out_pk(v[2 * e], v[2 * e + 1]);
-            l[e] = out_pk(v[2 * e] - out_lo16(h[e]), v[2 * e + 1] - out_hi16(h[e]));
+            h[e] = pk2(v[2 * e], v[2 * e + 1]);
+            l[e] = pk2(v[2 * e] - bf_lo(h[e]), v[2 * e + 1] - bf_hi(h[e]));
           }
           const bf16x8 xh = __builtin_bit_cast(bf16x8, make_uint4(h[0], h[1], h[2], h[3]));
           const bf16x8 xl = __builtin_bit_cast(bf16x8, make_uint4(l[0], l[1], l[2], l[3]));

@@ -32,14 +32,9 @@
 // ^ ((row >> 1) & 7)): every ds_read_b128 is conflict-free.  Per wave and
 // (tap, k-step): 4 filter + 4 position fragments for 16 MFMAs — the 1 : 2
 // LDS-read : MFMA issue ratio of the 3-D trunk kernel.
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int WT_I = 2, WT_R = 16, WT_C = 16;       // tile: images x rows x columns
 constexpr int WH_R = WT_R + 2, WH_C = WT_C + 2;     // 18 x 18 halo per image
@@ -54,20 +49,6 @@ constexpr int W_WE_OFF = W_EXO_OFF + WHP * 4;       // 159,520
 constexpr int W_LDS_EXO = W_WE_OFF + 9 * 64 * 4;    // 161,824
 constexpr int W_NT = 512;
 
-__device__ inline unsigned ws_pk(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
-__device__ inline float ws_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ inline float ws_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
-
-// LDS slab row rho = nf*16 + kq*4 + r  <->  output channel
-// (nf >> 1)*32 + kq*8 + (nf & 1)*4 + r  (kernels_conv_mfma_persist.hip)
-__device__ __host__ inline int ws_row_cout(int rho) {
-  const int nf = rho >> 4, kq = (rho >> 2) & 3, r = rho & 3;
-  return (nf >> 1) * 32 + kq * 8 + (nf & 1) * 4 + r;
-}
-
 // canonical fp32 w[tap 9][ci 64][co] -> bf16 images [ct][tap][rho 64][ci 64]
 // tail (C_out <= 16, one N fragment): rows 0 .. 15 are the channels in order
 // w_cin: channels of the canonical weights' C_in axis (64, or 65 with an
@@ -78,10 +59,10 @@ __global__ void pack_ws_kernel(const float* __restrict__ w, unsigned short* __re
   const int total = n_ct * 9 * 64 * 64;
   for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
     const int ci = idx & 63, rho = (idx >> 6) & 63, tap = (idx >> 12) % 9, ct = (idx >> 12) / 9;
-    const int co = tail ? (rho < 16 ? rho : cout) : ct * 64 + ws_row_cout(rho);
+    const int co = tail ? (rho < 16 ? rho : cout) : ct * 64 + slab_row_cout(rho);
     const float v = co < cout ? w[((size_t)tap * w_cin + ci) * cout + co] : 0.f;
     const int slot = (ci >> 3) ^ ((rho >> 1) & 7);
-    out[(((size_t)ct * 9 + tap) * 64 + rho) * 64 + slot * 8 + (ci & 7)] = (unsigned short)(ws_pk(v, 0.f) & 0xFFFFu);
+    out[(((size_t)ct * 9 + tap) * 64 + rho) * 64 + slot * 8 + (ci & 7)] = (unsigned short)(pk2(v, 0.f) & 0xFFFFu);
   }
   if (w_cin > 64) {
     float* we = reinterpret_cast<float*>(out + (size_t)total);
@@ -89,7 +70,7 @@ __global__ void pack_ws_kernel(const float* __restrict__ w, unsigned short* __re
       const int c = idx & 63, tap = (idx >> 6) % 9, ct = (idx >> 6) / 9;
       const int co = ct * 64 + c;
       const float v = co < cout ? w[((size_t)tap * w_cin + 64) * cout + co] : 0.f;
-      we[idx] = __uint_as_float(ws_pk(v, 0.f) << 16);
+      we[idx] = __uint_as_float(pk2(v, 0.f) << 16);
     }
   }
 }
@@ -255,8 +236,8 @@ __global__ __launch_bounds__(W_NT) void conv2d_ws_kernel(
 #define WS_ECOMMIT()                                                                            \
   if constexpr (EXO) {                                                                          \
     float* E_ = reinterpret_cast<float*>(smem + W_EXO_OFF);                                     \
-    E_[tid] = __uint_as_float(ws_pk(pe0, 0.f) << 16);                                           \
-    E_[tid + W_NT < WHP ? tid + W_NT : WHP - 1] = __uint_as_float(ws_pk(pe1, 0.f) << 16);       \
+    E_[tid] = __uint_as_float(pk2(pe0, 0.f) << 16);                                             \
+    E_[tid + W_NT < WHP ? tid + W_NT : WHP - 1] = __uint_as_float(pk2(pe1, 0.f) << 16);         \
   }
   float pe0 = 0.f, pe1 = 0.f;
   WS_FETCH(t_cur);
@@ -373,15 +354,12 @@ __global__ __launch_bounds__(W_NT) void conv2d_ws_kernel(
 // prefetch, the skip rows fetched at the top of T, the previous M's stores) is
 // at least a phase old.  tests/test_abi.py checks the compiled kernel for
 // scratch use and for any touch of an in-flight register.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ inline u32x4 pp_ld16(const void* p) {
   u32x4 v;
   asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
   return v;
 }
 constexpr int PH_BYTES = WH_R * WH_C * 128;     // 41,472: one image's halo
-
-#define PP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 template <bool RES>
 __global__ __launch_bounds__(W_NT) void conv2d_ws_pp_kernel(
@@ -493,7 +471,7 @@ __global__ __launch_bounds__(W_NT) void conv2d_ws_pp_kernel(
     *reinterpret_cast<u32x4*>(smem + ldsB) = PP_SEL(p9, 9);                                     \
     *reinterpret_cast<u32x4*>(smem + ldsC) = PP_SEL(p10, 10);                                   \
   }
-  // everything outstanding has landed; the "+v" operands pin every later use of
+  // everything outstanding has landed (not WAIT_VM(0)): the "+v" operands pin every later use of
   // the prefetch / skip registers behind this statement (volatile asm keeps
   // program order with the loads above and with the barriers)
 #define PP_WAIT_P()                                                                             \
@@ -529,7 +507,7 @@ __global__ __launch_bounds__(W_NT) void conv2d_ws_pp_kernel(
   PP_WAIT_P();
   PP_COMMIT();
   if (n_g > 1) PP_FETCH(t0 + grp + 2);
-  PP_BARRIER();
+  WG_BARRIER_LDS();
 
   // ---- fragment addresses (conv2d_ws_kernel): wave w of the group = rows 4 (w & 3) .. + 3
   const int w_row = (wave & 3) * 4;
@@ -565,12 +543,12 @@ __global__ __launch_bounds__(W_NT) void conv2d_ws_pp_kernel(
 
   const bool lin_cells = g.b == 1 && g.cpo == 64 && g.Cout - ct * 64 >= 64;
   f32x4 acc[4][4];
-  if (grp == 1) PP_BARRIER();      // half a period behind group 0
+  if (grp == 1) WG_BARRIER_LDS();      // half a period behind group 0
 #pragma unroll 1
   for (int k = 0; k < n_max; ++k) {
     if (k >= n_g) {     // (group 1 of an odd run: keeps the barrier count)
-      PP_BARRIER();
-      PP_BARRIER();
+      WG_BARRIER_LDS();
+      WG_BARRIER_LDS();
       continue;
     }
     int im, r0, c0;
@@ -659,7 +637,7 @@ __global__ __launch_bounds__(W_NT) void conv2d_ws_pp_kernel(
 #undef PP_FRAGS
       }
     }
-    PP_BARRIER();
+    WG_BARRIER_LDS();
 
     // =========================================================== M phase
     {
@@ -696,13 +674,13 @@ __global__ __launch_bounds__(W_NT) void conv2d_ws_pp_kernel(
             }
             if constexpr (RES) {
               const u32x4 q4 = rr[m][h];
-              v[0] += ws_lo(q4[0]); v[1] += ws_hi(q4[0]); v[2] += ws_lo(q4[1]); v[3] += ws_hi(q4[1]);
-              v[4] += ws_lo(q4[2]); v[5] += ws_hi(q4[2]); v[6] += ws_lo(q4[3]); v[7] += ws_hi(q4[3]);
+              v[0] += bf_lo(q4[0]); v[1] += bf_hi(q4[0]); v[2] += bf_lo(q4[1]); v[3] += bf_hi(q4[1]);
+              v[4] += bf_lo(q4[2]); v[5] += bf_hi(q4[2]); v[6] += bf_lo(q4[3]); v[7] += bf_hi(q4[3]);
             }
-            acc[m][2 * h][0] = __uint_as_float(ws_pk(v[0], v[1]));
-            acc[m][2 * h][1] = __uint_as_float(ws_pk(v[2], v[3]));
-            acc[m][2 * h][2] = __uint_as_float(ws_pk(v[4], v[5]));
-            acc[m][2 * h][3] = __uint_as_float(ws_pk(v[6], v[7]));
+            acc[m][2 * h][0] = __uint_as_float(pk2(v[0], v[1]));
+            acc[m][2 * h][1] = __uint_as_float(pk2(v[2], v[3]));
+            acc[m][2 * h][2] = __uint_as_float(pk2(v[4], v[5]));
+            acc[m][2 * h][3] = __uint_as_float(pk2(v[6], v[7]));
           }
         PP_WAIT_P();
         // stage 2: + second skip, stores
@@ -715,10 +693,10 @@ __global__ __launch_bounds__(W_NT) void conv2d_ws_pp_kernel(
           const unsigned o1z = __float_as_uint(acc[M][2 * (H)][2]), o1w = __float_as_uint(acc[M][2 * (H)][3]); \
           const u32x4 q4 = P;                                                                   \
           uint4 o;                                                                              \
-          o.x = ws_pk(ws_lo(o1x) + ws_lo(q4[0]), ws_hi(o1x) + ws_hi(q4[0]));                    \
-          o.y = ws_pk(ws_lo(o1y) + ws_lo(q4[1]), ws_hi(o1y) + ws_hi(q4[1]));                    \
-          o.z = ws_pk(ws_lo(o1z) + ws_lo(q4[2]), ws_hi(o1z) + ws_hi(q4[2]));                    \
-          o.w = ws_pk(ws_lo(o1w) + ws_lo(q4[3]), ws_hi(o1w) + ws_hi(q4[3]));                    \
+          o.x = pk2(bf_lo(o1x) + bf_lo(q4[0]), bf_hi(o1x) + bf_hi(q4[0]));                      \
+          o.y = pk2(bf_lo(o1y) + bf_lo(q4[1]), bf_hi(o1y) + bf_hi(q4[1]));                      \
+          o.z = pk2(bf_lo(o1z) + bf_lo(q4[2]), bf_hi(o1z) + bf_hi(q4[2]));                      \
+          o.w = pk2(bf_lo(o1w) + bf_lo(q4[3]), bf_hi(o1w) + bf_hi(q4[3]));                      \
           if (row_ok_ && ch_ok[H])                                                              \
             *reinterpret_cast<uint4*>(y + tbase + (unsigned long long)(unsigned)rc_ * RS + off_h[H]) = o; \
         }
@@ -745,11 +723,11 @@ __global__ __launch_bounds__(W_NT) void conv2d_ws_pp_kernel(
           const unsigned long long dst = tbase + (unsigned long long)(unsigned)rc * RS + off_h[h];
           if constexpr (RES) {
             const u32x4 q4 = rr[m][h];
-            v[0] += ws_lo(q4[0]); v[1] += ws_hi(q4[0]); v[2] += ws_lo(q4[1]); v[3] += ws_hi(q4[1]);
-            v[4] += ws_lo(q4[2]); v[5] += ws_hi(q4[2]); v[6] += ws_lo(q4[3]); v[7] += ws_hi(q4[3]);
+            v[0] += bf_lo(q4[0]); v[1] += bf_hi(q4[0]); v[2] += bf_lo(q4[1]); v[3] += bf_hi(q4[1]);
+            v[4] += bf_lo(q4[2]); v[5] += bf_hi(q4[2]); v[6] += bf_lo(q4[3]); v[7] += bf_hi(q4[3]);
           }
           uint4 o;
-          o.x = ws_pk(v[0], v[1]); o.y = ws_pk(v[2], v[3]); o.z = ws_pk(v[4], v[5]); o.w = ws_pk(v[6], v[7]);
+          o.x = pk2(v[0], v[1]); o.y = pk2(v[2], v[3]); o.z = pk2(v[4], v[5]); o.w = pk2(v[6], v[7]);
           if (!lin_st) {
             if (row_ok && ch_ok[h]) *reinterpret_cast<uint4*>(y + dst) = o;
           } else if (h == 0) {
@@ -779,9 +757,9 @@ __global__ __launch_bounds__(W_NT) void conv2d_ws_pp_kernel(
       }
       if (k + 2 < n_g && !(g.dbg & 1)) PP_FETCH(t0 + grp + 2 * (k + 2));
     }
-    PP_BARRIER();
+    WG_BARRIER_LDS();
   }
-  if (grp == 0) PP_BARRIER();
+  if (grp == 0) WG_BARRIER_LDS();
 }
 #undef PP_WAIT_ALL
 #undef PP_WAIT_P
@@ -793,7 +771,6 @@ __global__ __launch_bounds__(W_NT) void conv2d_ws_pp_kernel(
 #undef PP_LOADQ
 #undef PP_ADDRQ
 #undef PP_COL
-#undef PP_BARRIER
 
 // ---------------------------------------------------------------------------
 // The few-feature HEAD conv of a 2-D generator (C_in = 1 or 2 -> 64 channels,
@@ -839,7 +816,7 @@ __global__ __launch_bounds__(256) void conv2d_head_kernel(
   for (int j = 0; j < 8; ++j) bv[j] = bias ? bias[cg * 8 + j] : 0.f;
   const float slope = act == S3_ACT_LEAKY ? alpha : (act == S3_ACT_RELU ? 0.f : 1.f);
   auto rnd = [](float v) __attribute__((always_inline)) {
-    return F32 ? v : __uint_as_float(ws_pk(v, 0.f) << 16);
+    return F32 ? v : __uint_as_float(pk2(v, 0.f) << 16);
   };
 
   for (long long slot = (long long)blockIdx.x * 32 + (tid >> 3); slot < slots; slot += (long long)gridDim.x * 32) {
@@ -900,7 +877,7 @@ __global__ __launch_bounds__(256) void conv2d_head_kernel(
         yo += 128;
       } else {
         uint4 o;
-        o.x = ws_pk(acc[0], acc[1]); o.y = ws_pk(acc[2], acc[3]); o.z = ws_pk(acc[4], acc[5]); o.w = ws_pk(acc[6], acc[7]);
+        o.x = pk2(acc[0], acc[1]); o.y = pk2(acc[2], acc[3]); o.z = pk2(acc[4], acc[5]); o.w = pk2(acc[6], acc[7]);
         *reinterpret_cast<uint4*>(yo) = o;
         yo += 64;
       }
@@ -917,7 +894,7 @@ __global__ __launch_bounds__(256) void conv2d_head_kernel(
 // canonical fp32 w[tap 9][ci][co 64] -> the same layout with bf16-rounded values
 __global__ void pack_head_kernel(const float* __restrict__ w, float* __restrict__ out, int n, int exact) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = exact ? w[i] : __uint_as_float(ws_pk(w[i], 0.f) << 16);
+  if (i < n) out[i] = exact ? w[i] : __uint_as_float(pk2(w[i], 0.f) << 16);
 }
 
 }  // namespace

@@ -30,14 +30,9 @@
 // One 8-wave workgroup per CU walks a contiguous, XCD-major run of 2 images x 16
 // rows x 16 columns tiles.  MFMA time per tile and SIMD: 2 waves x 864 MFMAs x 16
 // clocks = 13.8 us at 2 GHz; the bf16 kernel moves the same cells in 4.6 us.
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int XT_I = 2, XT_R = 16, XT_C = 16;       // tile: images x rows x columns
 constexpr int XH_R = XT_R + 2, XH_C = XT_C + 2;     // 18 x 18 halo per image
@@ -49,23 +44,18 @@ constexpr int X_LDS = X_BIAS_OFF + 256;             // 156,928
 constexpr int X_NT = 512;
 constexpr int X_PASS_BYTES = 9 * 8192;              // one pass's filter image
 
-__device__ inline unsigned x3_pk(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
-__device__ inline float x3_lo16(unsigned u) { return __uint_as_float(u << 16); }
-__device__ inline float x3_hi16(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
-
 // eight fp32 channels -> one 16-B chunk of bf16 roundings (hi) and one of the
-// bf16-rounded residues v - hi (lo)
+// bf16-rounded residues v - hi (lo).  The arithmetic of the shared split8
+// (wave_prims.h) on raw dwords, kept here: through the shared one the four
+// conv2d_ws_x3 kernels allocate their registers differently.
 __device__ inline void x3_split8(const uint4 a, const uint4 b, uint4& hi, uint4& lo) {
   const float v[8] = {__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w),
                       __uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w)};
   unsigned h[4], l[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    h[e] = x3_pk(v[2 * e], v[2 * e + 1]);
-    l[e] = x3_pk(v[2 * e] - x3_lo16(h[e]), v[2 * e + 1] - x3_hi16(h[e]));
+    h[e] = pk2(v[2 * e], v[2 * e + 1]);
+    l[e] = pk2(v[2 * e] - bf_lo(h[e]), v[2 * e + 1] - bf_hi(h[e]));
   }
   hi = make_uint4(h[0], h[1], h[2], h[3]);
   lo = make_uint4(l[0], l[1], l[2], l[3]);
@@ -97,8 +87,8 @@ __global__ void pack_ws_x3_kernel(const float* __restrict__ w, unsigned short* _
     const int pass = r & 1, ct = r >> 1;
     const int co = ct * 64 + rho, ci = pass * 32 + x3_kperm(cl);
     const float v = co < cout ? w[((size_t)tap * 64 + ci) * cout + co] : 0.f;
-    const unsigned hi = x3_pk(v, 0.f) & 0xFFFFu;
-    const unsigned lo = x3_pk(v - __uint_as_float(hi << 16), 0.f) & 0xFFFFu;
+    const unsigned hi = pk2(v, 0.f) & 0xFFFFu;
+    const unsigned lo = pk2(v - __uint_as_float(hi << 16), 0.f) & 0xFFFFu;
     const int sw = (rho >> 1) & 7;
     unsigned short* o = out + ((((size_t)ct * 2 + pass) * 9 + tap) * 64 + rho) * 64;
     o[((cl >> 3) ^ sw) * 8 + (cl & 7)] = (unsigned short)hi;
@@ -287,7 +277,7 @@ __global__ __launch_bounds__(X_NT) void conv2d_ws_x3_kernel(
     }
     X3_TAPS()
     // every wave's fragment reads are back before the halo and the slabs are rewritten
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    WG_BARRIER_LDS();
     pass = 1 - pass;
     X3_LOAD_IMAGE(pass);
     X3_COMMIT();
@@ -297,7 +287,7 @@ __global__ __launch_bounds__(X_NT) void conv2d_ws_x3_kernel(
     if (has_next && !(g.dbg & 1)) X3_FETCH(t_cur + 1, next_first);
     X3_TAPS()
     if (has_next) {
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      WG_BARRIER_LDS();
       if (next_first != pass) {
         pass = next_first;
         X3_LOAD_IMAGE(pass);
@@ -341,7 +331,6 @@ __global__ __launch_bounds__(X_NT) void conv2d_ws_x3_kernel(
 #undef X3_FETCH
 #undef X3_FETCH1
 }
-
 
 // ---------------------------------------------------------------------------
 // Ping-pong form.  In the kernel above all eight waves walk the same phases
@@ -521,7 +510,6 @@ __global__ __launch_bounds__(X_NT) void conv2d_ws_x3_pp_kernel(
           acc[m][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[nf], ph[m], acc[m][nf], 0, 0, 0); \
     }                                                                                           \
   }
-#define PX_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
   f32x4 acc[4][4];
 #pragma unroll
@@ -568,7 +556,7 @@ __global__ __launch_bounds__(X_NT) void conv2d_ws_x3_pp_kernel(
       }
     }
     if (r == n_rounds) break;                            // (group 1's last M was the tail)
-    PX_BARRIER();
+    WG_BARRIER_LDS();
     // ---------------- phase Y: group 1 in T (round r), group 0 in M (after its T of round r)
     const bool swap = r + 1 < n_rounds && !(g.dbg & 8);
     if (grp == 1) {
@@ -590,14 +578,13 @@ __global__ __launch_bounds__(X_NT) void conv2d_ws_x3_pp_kernel(
         }
       }
     }
-    PX_BARRIER();
+    WG_BARRIER_LDS();
     // ---------------- the image of the next round's pass
     if (swap) {
       PX_LOAD_IMAGE(1 - p);
-      PX_BARRIER();
+      WG_BARRIER_LDS();
     }
   }
-#undef PX_BARRIER
 #undef PX_TAPS
 #undef PX_LOAD_IMAGE
 #undef PX_COMMIT

@@ -17,14 +17,9 @@
 // the C_in values of 16 consecutive t: one contiguous store per fragment.
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int DT0 = 4, DT1 = 8, DT2 = 16;
 constexpr int DH0 = DT0 + 2, DH1 = DT1 + 2, DH2 = DT2 + 2;
@@ -32,11 +27,6 @@ constexpr int DHP = DH0 * DH1 * DH2;         // 1080 halo cells
 constexpr int DNW = 4;                       // waves; 8 (s1, s2) rows each
 constexpr int DNT = DNW * 64;
 constexpr int DLDS = DHP * 64;               // 69,120 B
-
-__device__ __forceinline__ unsigned pk2(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
 
 // fp32 w[tap][cin][32] -> bf16 img[tap'][16 rows][32], tap' = 26 - tap, rows >= cin zero
 __global__ void dgrad_c2_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ img,
@@ -182,7 +172,6 @@ __global__ __launch_bounds__(DNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-
 // ---------------------------------------------------------------------------
 // Round 3: the same gradient as a SLIDING WINDOW with the three t-taps packed
 // into the MFMA's M dimension.
@@ -263,7 +252,6 @@ __global__ __launch_bounds__(GNT) void conv_dgrad_c2_slide_kernel(
     r0 = (tr % segs0) * GSEG0; tr /= segs0;
     n = tr;
   };
-#define GSL_BARRIER() asm volatile("s_barrier" ::: "memory")
 
   if (wave >= GNCW) {
     // ---------------------------------------------------- staging waves
@@ -292,14 +280,14 @@ __global__ __launch_bounds__(GNT) void conv_dgrad_c2_slide_kernel(
     const int plane_ops = (GP1 - sw + GNDW - 1) / GNDW;     // 5 or 4
     auto wait_planes = [&](int in_flight) __attribute__((always_inline)) {
       switch (in_flight * plane_ops) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+        case 0: WAIT_VM(0); break;
+        case 4: WAIT_VM(4); break;
+        case 5: WAIT_VM(5); break;
+        case 8: WAIT_VM(8); break;
+        case 10: WAIT_VM(10); break;
+        case 12: WAIT_VM(12); break;
+        case 15: WAIT_VM(15); break;
+        default: WAIT_VM(0); break;
       }
     };
     for (int u = u_first; u < u_end; u += u_step) {
@@ -312,13 +300,13 @@ __global__ __launch_bounds__(GNT) void conv_dgrad_c2_slide_kernel(
       for (; issued < 2 + GPD && issued < rows + 2; ++issued)
         stage_plane(n, r0 + issued, o1, o2, issued % GNSLOT);
       wait_planes(issued - 3 > 0 ? issued - 3 : 0);          // planes 0 .. 2 are in
-      GSL_BARRIER();
+      WG_BARRIER();
       for (int r = 0; r < rows; ++r) {
         // slot (r + 2 + GPD) % GNSLOT held plane r - 1: free since the last barrier
         if (issued < rows + 2) { stage_plane(n, r0 + issued, o1, o2, issued % GNSLOT); ++issued; }
         const int need = r + 4 < rows + 2 ? r + 4 : rows + 2;   // row r + 1 reads planes up to r + 3
         wait_planes(issued - need);
-        GSL_BARRIER();
+        WG_BARRIER();
       }
     }
     return;
@@ -335,7 +323,7 @@ __global__ __launch_bounds__(GNT) void conv_dgrad_c2_slide_kernel(
     int n, r0, o1, o2;
     unit_org(u, n, r0, o1, o2);
     const int rows = (r0 + GSEG0 <= g.D[0] ? GSEG0 : g.D[0] - r0);
-    GSL_BARRIER();
+    WG_BARRIER();
     for (int r = 0; r < rows; ++r) {
       f32x4 acc[2];
 #pragma unroll
@@ -368,10 +356,9 @@ __global__ __launch_bounds__(GNT) void conv_dgrad_c2_slide_kernel(
           *reinterpret_cast<float2*>(dst) = make_float2(acc[m][0] + s10 + s20, acc[m][1] + s11 + s21);
         }
       }
-      GSL_BARRIER();
+      WG_BARRIER();
     }
   }
-#undef GSL_BARRIER
 }
 
 }  // namespace

@@ -17,14 +17,9 @@
 // class but re-reads every dPre cell through L1 (1.31 ms at C2 batch 8).
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int ST0 = 4, ST1 = 8, ST2 = 16;
 constexpr int SG0 = ST0 + 1, SG1 = ST1 + 1, SG2 = ST2 + 1;
@@ -32,11 +27,6 @@ constexpr int SHP = SG0 * SG1 * SG2;          // 765 halo cells
 constexpr int SNW = 4;
 constexpr int SNT = SNW * 64;
 constexpr int SLDS = SHP * 64;                // 48,960 B
-
-__device__ __forceinline__ unsigned pk2(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
 
 // fp32 w[tap][cin][32] -> bf16 img[tap][cin_pad][32]  (rows = ci, K = co)
 __global__ void dgrad_s2_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ img,

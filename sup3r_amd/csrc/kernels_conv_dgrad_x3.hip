@@ -21,27 +21,10 @@
 // comments explain them); per (tap, fragment) three MFMAs, small terms first.
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pk2(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
-__device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
-// eight fp32 values -> their hi and lo bf16 halves (16 B each)
-__device__ __forceinline__ void split8(const float4& a, const float4& b, uint4& hi, uint4& lo) {
-  hi = make_uint4(pk2(a.x, a.y), pk2(a.z, a.w), pk2(b.x, b.y), pk2(b.z, b.w));
-  lo = make_uint4(pk2(a.x - bf_lo(hi.x), a.y - bf_hi(hi.x)), pk2(a.z - bf_lo(hi.y), a.w - bf_hi(hi.y)),
-                  pk2(b.x - bf_lo(hi.z), b.y - bf_hi(hi.z)), pk2(b.z - bf_lo(hi.w), b.w - bf_hi(hi.w)));
-}
 #define MFMA3(acc, ah, al, bh, bl)                                              \
   do {                                                                          \
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);        \

@@ -18,17 +18,11 @@
 //
 // The weight gradient has no reduction over channels: one thread per
 // (tap, ci, co) walks the positions (dPre rows coalesced along co).
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
 
 constexpr int PB = 8;   // positions per block
-
-__device__ inline float act_f(float v, int act, float alpha) {
-  if (act == S3_ACT_RELU) return v > 0.f ? v : 0.f;
-  if (act == S3_ACT_LEAKY) return v > 0.f ? v : alpha * v;
-  return v;
-}
 
 // mode 0: forward  (rows = output positions of g, src = input cells)
 // mode 1: dgrad    (rows = input positions of g,  src = output cells)
@@ -142,7 +136,7 @@ __global__ void fewpos_epilogue_kernel(const float* __restrict__ partial,
       dst = ((((int64_t)n * g.O[0] * b + o0 * b + blk / b) * (g.O[1] * b) +
               o1 * b + blk % b) * g.O[2] + o2) * cpo + cc;
     }
-    t = act_f(t, g.act, g.alpha);
+    t = act_f_branch(t, g.act, g.alpha);
     if (res) t += res[dst];
     y[dst] = t;
   }

@@ -25,21 +25,13 @@
 //
 // Every output element is a fixed-order sum that does not depend on the batch
 // size or on which other positions share its workgroup.
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MAX_TAPS = 27;
 constexpr int NW = 8;          // waves per workgroup (they split the reduction axis)
 constexpr int NT = NW * 64;
-
-__device__ inline float actf(float v, int act, float alpha) {
-  if (act == S3_ACT_RELU) return v > 0.f ? v : 0.f;
-  if (act == S3_ACT_LEAKY) return v > 0.f ? v : alpha * v;
-  return v;
-}
 
 // source cell of row `row` under tap `tap` (-1: padding / no contribution)
 // MODE 0: row = output position, source = input cell
@@ -178,7 +170,7 @@ __global__ __launch_bounds__(NT) void fewpos_mfma_kernel(
   }
   if (bias) v += *reinterpret_cast<const f32x4*>(bias + n);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = actf(v[e], g.act, g.alpha);
+  for (int e = 0; e < 4; ++e) v[e] = act_f_branch(v[e], g.act, g.alpha);
   const int b = g.d2s;
   if (b <= 1) {
     const int64_t dst = (int64_t)grow * Nc + n;
@@ -298,7 +290,7 @@ __device__ __forceinline__ void mfma16_body(
     return;
   }
   if (bias) v += bias[n];
-  v = actf(v, g.act, g.alpha);
+  v = act_f_branch(v, g.act, g.alpha);
   int64_t dst = (int64_t)grow * Nc + n;
   const int b = g.d2s;
   if (b > 1) {

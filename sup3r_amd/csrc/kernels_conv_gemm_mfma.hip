@@ -28,33 +28,24 @@
 // stores, 64 contiguous bytes per position across the 4 k-groups.
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int GT_N = 64;       // output-channel tile (4 fragments)
 constexpr int GT_WAVES = 4;
 
-__device__ inline unsigned pk2(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
-__device__ inline bf16x8 pack8(const float4& a, const float4& b) {
+__device__ __forceinline__ bf16x8 pack8(const float4& a, const float4& b) {
   uint4 u = make_uint4(pk2(a.x, a.y), pk2(a.z, a.w), pk2(b.x, b.y), pk2(b.z, b.w));
   return __builtin_bit_cast(bf16x8, u);
 }
-// the same with the rounding residue: hi = bf16(v), lo = bf16(v - hi)
+// the same with the rounding residue: hi = bf16(v), lo = bf16(v - hi).  The
+// arithmetic of the shared split8 (wave_prims.h), kept here: as a wrapper over
+// it the X3 instantiations of gconv_mfma_kernel schedule differently.
 __device__ inline void split8(const float4& a, const float4& b, bf16x8& hi, bf16x8& lo) {
   const uint4 h = make_uint4(pk2(a.x, a.y), pk2(a.z, a.w), pk2(b.x, b.y), pk2(b.z, b.w));
-  auto lo_f = [](unsigned u) { return __uint_as_float(u << 16); };
-  auto hi_f = [](unsigned u) { return __uint_as_float(u & 0xFFFF0000u); };
-  const uint4 l = make_uint4(pk2(a.x - lo_f(h.x), a.y - hi_f(h.x)), pk2(a.z - lo_f(h.y), a.w - hi_f(h.y)),
-                             pk2(b.x - lo_f(h.z), b.y - hi_f(h.z)), pk2(b.z - lo_f(h.w), b.w - hi_f(h.w)));
+  const uint4 l = make_uint4(pk2(a.x - bf_lo(h.x), a.y - bf_hi(h.x)), pk2(a.z - bf_lo(h.y), a.w - bf_hi(h.y)),
+                             pk2(b.x - bf_lo(h.z), b.y - bf_hi(h.z)), pk2(b.z - bf_lo(h.w), b.w - bf_hi(h.w)));
   hi = __builtin_bit_cast(bf16x8, h);
   lo = __builtin_bit_cast(bf16x8, l);
 }
@@ -372,7 +363,6 @@ __global__ __launch_bounds__(GT_WAVES * 64) void gconv_mfma_kernel(
   }
 }
 
-
 // sums the slices of a split contraction in fixed order, then the forward
 // epilogue (bias, activation, residual, fp32 or bf16 store) or the data
 // gradient's plain / accumulating store
@@ -646,15 +636,13 @@ __global__ __launch_bounds__(FHW * 64) void gconv_fewch_halo_kernel(
     }
     const bool ok = hp < FHP && i0 >= 0 && i0 < D0 && i1 >= 0 && i1 < D1 && i2 >= 0 && i2 < D2;
     const float* src = x + ((((int64_t)n * D0 + i0) * D1 + i1) * D2 + i2) * CIN;
-    auto lo_f = [](unsigned u) { return __uint_as_float(u << 16); };
-    auto hi_f = [](unsigned u) { return __uint_as_float(u & 0xFFFF0000u); };
     if (CIN == 2) {
       float2 t = make_float2(0.f, 0.f);
       if (ok) t = *reinterpret_cast<const float2*>(src);
       const unsigned h = pk2(t.x, t.y);
       *reinterpret_cast<unsigned*>(halo + hp * CELLB) = h;
       if constexpr (X3)
-        *reinterpret_cast<unsigned*>(halo + LO_IMG + hp * CELLB) = pk2(t.x - lo_f(h), t.y - hi_f(h));
+        *reinterpret_cast<unsigned*>(halo + LO_IMG + hp * CELLB) = pk2(t.x - bf_lo(h), t.y - bf_hi(h));
     } else {
       float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
       if (ok) t = *reinterpret_cast<const float4*>(src);
@@ -662,7 +650,7 @@ __global__ __launch_bounds__(FHW * 64) void gconv_fewch_halo_kernel(
       *reinterpret_cast<uint2*>(halo + hp * CELLB) = make_uint2(h0, h1);
       if constexpr (X3)
         *reinterpret_cast<uint2*>(halo + LO_IMG + hp * CELLB) =
-            make_uint2(pk2(t.x - lo_f(h0), t.y - hi_f(h0)), pk2(t.z - lo_f(h1), t.w - hi_f(h1)));
+            make_uint2(pk2(t.x - bf_lo(h0), t.y - bf_hi(h0)), pk2(t.z - bf_lo(h1), t.w - bf_hi(h1)));
     }
   }
   // this lane's taps: chunk kc, slot q -> tap = (kc*32 + kq*8) / CIN + q; byte offset

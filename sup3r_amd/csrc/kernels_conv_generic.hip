@@ -14,16 +14,9 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-__device__ inline float act_f(float v, int act, float alpha) {
-  // one select for every kind (slope 1 = identity, 0 = ReLU, alpha = Leaky):
-  // testing the kind per element compiles to two scalar branches per value
-  const float s = act == S3_ACT_LEAKY ? alpha : (act == S3_ACT_RELU ? 0.f : 1.f);
-  return v > 0.f ? v : s * v;
-}
 
 __device__ inline int src_index(int o, int t, int stride, int lo, int n,
                                 int pad_mode, bool& valid) {

@@ -13,14 +13,9 @@
 // (t, kg) stores 4 consecutive output channels per fragment.
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int HT0 = 4, HT1 = 8, HT2 = 16;
 constexpr int HH0 = HT0 + 2, HH1 = HT1 + 2, HH2 = HT2 + 2;
@@ -28,11 +23,6 @@ constexpr int HHP = HH0 * HH1 * HH2;         // 1080 halo cells
 constexpr int HNW = 4;
 constexpr int HNT = HNW * 64;
 constexpr int HLDS = HHP * 64;               // 69,120 B
-
-__device__ __forceinline__ unsigned pk2(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
 
 // fp32 w[tap][32][cout] -> bf16 img[tap][rows_pad][32]
 __global__ void halo32_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ img,

@@ -26,14 +26,9 @@
 // (t, kg) of the C/D fragment owns 4 consecutive output channels.
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int ST0 = 2, ST1 = 4, ST2 = 16;                 // output tile
 constexpr int SH0 = 2 * ST0 + 1, SH1 = 2 * ST1 + 1, SH2 = 2 * ST2 + 1;   // 5 x 9 x 33
@@ -44,11 +39,6 @@ constexpr int S_FILT = 27 * 32 * 64;                      // 55,296 B
 constexpr int S_LDS = S_HALO + S_FILT;                    // 150,336 B
 constexpr int SNCH = (SHP * 4 + SNT - 1) / SNT;           // 12 chunks per lane
 constexpr int NEVEN = ST2 + 1;                            // even cells of a row
-
-__device__ __forceinline__ unsigned pk2(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
 
 // in-row slot of input cell c2 (de-interleaved) and the chunk swizzle key
 __device__ __forceinline__ int row_slot(int c2) { return (c2 & 1) ? NEVEN + (c2 >> 1) : (c2 >> 1); }
@@ -209,7 +199,6 @@ __global__ __launch_bounds__(SNT) void conv_halo_s2_kernel(
     __syncthreads();
   }
 }
-
 
 // ---------------------------------------------------------------------------
 // C_in = C_out = 64 (the discriminator's 64 -> 64 stride-2 layer: 35 GFLOP at

@@ -33,14 +33,9 @@
 // 7), slab chunk ^ ((row >> 1) & 7)); all ds_read_b128 are conflict-free.
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int TS0 = 4, TS1 = 8, TS2 = 16;
 constexpr int H0 = TS0 + 2, H1 = TS1 + 2, H2 = TS2 + 2;
@@ -94,33 +89,9 @@ struct PGeo {
   static constexpr int halo_k(int t) { return early_k(t) + late_k(t); }
 };
 
-__device__ inline unsigned pk_bf16(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
-__device__ inline float lo_f(unsigned u) { return __uint_as_float(u << 16); }
-__device__ inline float hi_f(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
-
-// LDS slab row rho = nf*16 + kq*4 + r  <->  output channel
-//   (nf >> 1)*32 + kq*8 + (nf & 1)*4 + r
-// so that lane (pos, kq) owns channels h*32 + kq*8 .. +7 for h = nf >> 1.
-__device__ __host__ inline int slab_row_cout(int rho) {
-  const int nf = rho >> 4, kq = (rho >> 2) & 3, r = rho & 3;
-  return (nf >> 1) * 32 + kq * 8 + (nf & 1) * 4 + r;
-}
-
-// workgroup barrier without the fence of __syncthreads(): LDS hand-over is
-// ordered by the explicit waits next to it ("memory": no compiler motion)
-#define WG_BARRIER() asm volatile("s_barrier" ::: "memory")
-#define WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-template <int N>
-__device__ inline void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // 16-B global load the compiler can neither sink nor wait on: the producer
 // loop orders it by hand (asm volatile keeps program order with the counted
 // s_waitcnt / s_barrier statements).  saddr + 32-bit byte offset.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ inline u32x4 ld16_async(const void* sbase, unsigned voff) {
   u32x4 v;
   asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(voff), "s"(sbase) : "memory");
@@ -129,13 +100,13 @@ __device__ inline u32x4 ld16_async(const void* sbase, unsigned voff) {
 // n is a constant after unrolling: the switch folds to one s_waitcnt
 __device__ inline void wait_vm_n(int n) {
   switch (n) {
-    case 0: wait_vm<0>(); break;
-    case 1: wait_vm<1>(); break;
-    case 2: wait_vm<2>(); break;
-    case 3: wait_vm<3>(); break;
-    case 4: wait_vm<4>(); break;
-    case 5: wait_vm<5>(); break;
-    default: wait_vm<6>(); break;
+    case 0: WAIT_VM(0); break;
+    case 1: WAIT_VM(1); break;
+    case 2: WAIT_VM(2); break;
+    case 3: WAIT_VM(3); break;
+    case 4: WAIT_VM(4); break;
+    case 5: WAIT_VM(5); break;
+    default: WAIT_VM(6); break;
   }
 }
 
@@ -149,7 +120,7 @@ __global__ void pack_persist_kernel(const float* __restrict__ w,
     const int ci = idx & 63, rho = (idx >> 6) & 63, tap = (idx >> 12) % 27, ct = (idx >> 12) / 27;
     const int co = ct * 64 + slab_row_cout(rho);
     const float v = co < cout ? w[((size_t)tap * 64 + ci) * cout + co] : 0.f;
-    const unsigned u = pk_bf16(v, 0.f);
+    const unsigned u = pk2(v, 0.f);
     const int slot = (ci >> 3) ^ ((rho >> 1) & 7);
     out[(((size_t)ct * 27 + tap) * 64 + rho) * 64 + slot * 8 + (ci & 7)] = (unsigned short)(u & 0xFFFFu);
   }
@@ -174,7 +145,7 @@ __global__ void pack_jobs_kernel(const S3PackJob* __restrict__ jobs) {
     if (co < jb.cout)
       v = jb.dgrad ? jb.w[((size_t)(26 - tap) * jb.cout + co) * 64 + ci]      // forward w[tap][ci_f = co'][co_f = ci']
                    : jb.w[((size_t)tap * 64 + ci) * jb.cout + co];
-    const unsigned short h = (unsigned short)(pk_bf16(v, 0.f) & 0xFFFFu);
+    const unsigned short h = (unsigned short)(pk2(v, 0.f) & 0xFFFFu);
     const size_t base = (((size_t)ct * 27 + tap) * 64) * 64;
     const int sw = (ci >> 3);
     jb.tile[base + (size_t)row * 64 + ((sw ^ ((row >> 1) & 7)) << 3) + (ci & 7)] = h;
@@ -415,12 +386,12 @@ __global__ __launch_bounds__(NTHR) void conv3_mfma_persist_kernel(
       for (int r = 0; r < H0; ++r) {
 #pragma unroll
         for (int j = 0; j < JR; ++j) hrow[j] = halo_load(r, j);
-        wait_vm<0>();
+        WAIT_VM(0);
 #pragma unroll
         for (int j = 0; j < JR; ++j) halo_put(r, j, hrow[j]);
       }
     }
-    wait_vm<0>();
+    WAIT_VM(0);
     WAIT_LGKM0();
     WG_BARRIER();
 
@@ -601,8 +572,8 @@ __global__ __launch_bounds__(NTHR) void conv3_mfma_persist_kernel(
           f32x4 a0 = acc[m][(2 * h) % NFV], a1 = acc[m][(2 * h + 1) % NFV];
           if constexpr (F16) {
             uint4 o;
-            o.x = pk_bf16(a0[0], a0[1]); o.y = pk_bf16(a0[2], a0[3]);
-            o.z = pk_bf16(a1[0], a1[1]); o.w = pk_bf16(a1[2], a1[3]);
+            o.x = pk2(a0[0], a0[1]); o.y = pk2(a0[2], a0[3]);
+            o.z = pk2(a1[0], a1[1]); o.w = pk2(a1[2], a1[3]);
             *reinterpret_cast<uint4*>(y + yo + h * 32) = o;
             continue;
           }
@@ -686,12 +657,12 @@ __global__ __launch_bounds__(NTHR) void conv3_mfma_persist_kernel(
         }
         if (res) {
           const uint4 r = rres[m][h];
-          v[0] += lo_f(r.x); v[1] += hi_f(r.x); v[2] += lo_f(r.y); v[3] += hi_f(r.y);
-          v[4] += lo_f(r.z); v[5] += hi_f(r.z); v[6] += lo_f(r.w); v[7] += hi_f(r.w);
+          v[0] += bf_lo(r.x); v[1] += bf_hi(r.x); v[2] += bf_lo(r.y); v[3] += bf_hi(r.y);
+          v[4] += bf_lo(r.z); v[5] += bf_hi(r.z); v[6] += bf_lo(r.w); v[7] += bf_hi(r.w);
         }
         uint4 o;
-        o.x = pk_bf16(v[0], v[1]); o.y = pk_bf16(v[2], v[3]);
-        o.z = pk_bf16(v[4], v[5]); o.w = pk_bf16(v[6], v[7]);
+        o.x = pk2(v[0], v[1]); o.y = pk2(v[2], v[3]);
+        o.z = pk2(v[4], v[5]); o.w = pk2(v[6], v[7]);
         *reinterpret_cast<uint4*>(y + e_base + off) = o;
       }
     }

@@ -32,15 +32,9 @@
 // (tests/test_parity_r04.py).
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TS0 = 4, TS1 = 8, TS2 = 16;
 constexpr int H0 = TS0 + 2, H1 = TS1 + 2, H2 = TS2 + 2;
@@ -57,17 +51,6 @@ constexpr int PT = NPW * 64;
 constexpr int ROWC = H1 * H2;                    // 180 cells per halo row
 constexpr int JR = (ROWC * 8 + PT - 1) / PT;     // 6 chunks per row per producer lane
 constexpr int ARING = 4;                         // A fragments in flight ahead of the MFMAs
-
-__device__ inline unsigned pk_bf16(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
-__device__ inline float lo_f(unsigned u) { return __uint_as_float(u << 16); }
-__device__ inline float hi_f(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
-
-#define WG_BARRIER() asm volatile("s_barrier" ::: "memory")
-#define WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define WAIT_VM0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
 // NFV / ct / bias / res / depth-to-space store: as conv3_mfma_persist_kernel
 // (plain forward only here: no DG frames, no fused temporal repeat).
@@ -344,12 +327,12 @@ __global__ __launch_bounds__(NTHR) void conv3_mfma_persist2_kernel(
           }
           if (res) {
             const uint4 r = rres[q][hh];
-            v[0] += lo_f(r.x); v[1] += hi_f(r.x); v[2] += lo_f(r.y); v[3] += hi_f(r.y);
-            v[4] += lo_f(r.z); v[5] += hi_f(r.z); v[6] += lo_f(r.w); v[7] += hi_f(r.w);
+            v[0] += bf_lo(r.x); v[1] += bf_hi(r.x); v[2] += bf_lo(r.y); v[3] += bf_hi(r.y);
+            v[4] += bf_lo(r.z); v[5] += bf_hi(r.z); v[6] += bf_lo(r.w); v[7] += bf_hi(r.w);
           }
           uint4 o;
-          o.x = pk_bf16(v[0], v[1]); o.y = pk_bf16(v[2], v[3]);
-          o.z = pk_bf16(v[4], v[5]); o.w = pk_bf16(v[6], v[7]);
+          o.x = pk2(v[0], v[1]); o.y = pk2(v[2], v[3]);
+          o.z = pk2(v[4], v[5]); o.w = pk2(v[6], v[7]);
           *reinterpret_cast<uint4*>(y + e_base + e_pos[q] + c_off[hh]) = o;
         }
     }

@@ -25,14 +25,9 @@
 // cores.  One raw s_barrier per tile hands the buffers over.
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int T0 = 4, T1 = 8, T2 = 64;
 constexpr int H0 = T0 + 2, H1 = T1 + 2, H2 = T2 + 2;
@@ -44,19 +39,6 @@ constexpr int NDMA = (HP + 63) / 64;             // 62 wave-instructions per hal
 constexpr int BUF_BYTES = NDMA * 64 * 16;        // 63,488 (tail lanes land in the pad)
 constexpr int GROUPS = T0 * T1 * (T2 / 16);      // 128 fragments of 16 positions
 constexpr int KS = 7;                            // ceil(27 / 4) k-steps
-
-__device__ inline unsigned pk2(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
-__device__ inline float act_sel(float v, float slope) { return v > 0.f ? v : slope * v; }
-// (x * scale) + shift with two roundings, like numpy's un-normalisation
-// (s3_chunk_epilogue does the same): the windowed forward of the C3 executor
-__device__ inline float affine2(float v, float sc, float sh) {
-  float t = v * sc;
-  asm volatile("" : "+v"(t));
-  return t + sh;
-}
 
 // BAND (C_out == 2 only): the 16 MFMA rows are 8 consecutive output positions
 // x 2 channels instead of 2 channels + 14 rows of padding — see the compute
@@ -186,7 +168,6 @@ __global__ __launch_bounds__(NTH) void conv_tail_mfma_kernel(
 
   // raw workgroup barrier: the hand-over is ordered by the staging waves'
   // own vmcnt(0) before it ("memory": no compiler motion across it)
-#define TAIL_BARRIER() asm volatile("s_barrier" ::: "memory")
   int cur = 0;
   if (wave >= NCW) {
     // ---------------------------------------------------- staging waves
@@ -199,19 +180,19 @@ __global__ __launch_bounds__(NTH) void conv_tail_mfma_kernel(
             make_uint4(0, 0, 0, 0);
     }
     if (t_first < t_end) stage(t_first, 0);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    TAIL_BARRIER();
+    WAIT_VM_LGKM0(0);
+    WG_BARRIER();
     for (int tile = t_first; tile < t_end; tile += t_step) {
       const int next = tile + t_step;
       if (next < t_end) stage(next, cur ^ 1);
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      TAIL_BARRIER();   // next halo landed, this one free
+      WAIT_VM_LGKM0(0);
+      WG_BARRIER();   // next halo landed, this one free
       cur ^= 1;
     }
     return;
   }
   // ------------------------------------------------------ compute waves
-  TAIL_BARRIER();
+  WG_BARRIER();
   for (int tile = t_first; tile < t_end; tile += t_step) {
     int n, org0, org1, org2;
     tile_org(tile, n, org0, org1, org2);
@@ -312,8 +293,7 @@ __global__ __launch_bounds__(NTH) void conv_tail_mfma_kernel(
         if (o0 < g.O[0] && o1 < g.O[1] && o2 < g.O[2]) {
           float* yp = y + ((((size_t)n * g.O[0] + o0) * g.O[1] + o1) * g.O[2] + o2) * 2;
           // (the model output is never re-read on the device)
-          typedef float f32x2 __attribute__((ext_vector_type(2)));
-          __builtin_nontemporal_store((f32x2){v0, v1}, reinterpret_cast<f32x2*>(yp));
+          __builtin_nontemporal_store((hf32x2){v0, v1}, reinterpret_cast<hf32x2*>(yp));
         }
       } else {
 #pragma unroll
@@ -336,12 +316,10 @@ __global__ __launch_bounds__(NTH) void conv_tail_mfma_kernel(
       }
     }
     }   // !BAND
-    TAIL_BARRIER();
+    WG_BARRIER();
     cur ^= 1;
   }
-#undef TAIL_BARRIER
 }
-
 
 // ---------------------------------------------------------------------------
 // Sliding-window variant for C_out = 2 (the banded form above): the kernel is
@@ -430,14 +408,14 @@ __global__ __launch_bounds__(NTH) void conv_tail_slide_kernel(
   auto wait_planes = [&](int in_flight) __attribute__((always_inline)) {
     // all but the youngest `in_flight` planes of this wave have landed
     switch (in_flight * plane_ops) {
-      case 0: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); break;
-      case 8: asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory"); break;
-      case 10: asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory"); break;
-      case 16: asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory"); break;
-      case 20: asm volatile("s_waitcnt vmcnt(20) lgkmcnt(0)" ::: "memory"); break;
-      case 24: asm volatile("s_waitcnt vmcnt(24) lgkmcnt(0)" ::: "memory"); break;
-      case 30: asm volatile("s_waitcnt vmcnt(30) lgkmcnt(0)" ::: "memory"); break;
-      default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); break;
+      case 0: WAIT_VM_LGKM0(0); break;
+      case 8: WAIT_VM_LGKM0(8); break;
+      case 10: WAIT_VM_LGKM0(10); break;
+      case 16: WAIT_VM_LGKM0(16); break;
+      case 20: WAIT_VM_LGKM0(20); break;
+      case 24: WAIT_VM_LGKM0(24); break;
+      case 30: WAIT_VM_LGKM0(30); break;
+      default: WAIT_VM_LGKM0(0); break;
     }
   };
 
@@ -461,7 +439,6 @@ __global__ __launch_bounds__(NTH) void conv_tail_slide_kernel(
   }
   const float slope = g.act == S3_ACT_LEAKY ? g.alpha : (g.act == S3_ACT_RELU ? 0.f : 1.f);
   const float b0 = bias ? bias[0] : 0.f, b1 = bias ? bias[1] : 0.f;
-#define SLIDE_BARRIER() asm volatile("s_barrier" ::: "memory")
 
   if (wave >= NCW) {
     // ---------------------------------------------------- staging waves
@@ -482,14 +459,14 @@ __global__ __launch_bounds__(NTH) void conv_tail_slide_kernel(
       int issued = 0;                        // planes staged so far
       for (; issued < 2 + PD && issued < rows + 2; ++issued) stage_plane(n, r0 + issued, o1, o2, issued % NSLOT);
       wait_planes(issued - 3);               // planes 0 .. 2 are in
-      SLIDE_BARRIER();
+      WG_BARRIER();
       for (int r = 0; r < rows; ++r) {
         // slot (r + 2 + PD) % NSLOT held plane r - 1: free since the last barrier
         if (issued < rows + 2) { stage_plane(n, r0 + issued, o1, o2, issued % NSLOT); ++issued; }
         // row r + 1 reads planes up to r + 3
         const int need = r + 4 < rows + 2 ? r + 4 : rows + 2;
         wait_planes(issued - need);
-        SLIDE_BARRIER();                     // row r computed, plane r + 3 landed
+        WG_BARRIER();                     // row r computed, plane r + 3 landed
       }
     }
     return;
@@ -502,7 +479,7 @@ __global__ __launch_bounds__(NTH) void conv_tail_slide_kernel(
     int n, r0, o1, o2;
     unit_org(u, n, r0, o1, o2);
     const int rows = (r0 + SEG0 <= g.O[0] ? SEG0 : g.O[0] - r0);
-    SLIDE_BARRIER();
+    WG_BARRIER();
     for (int r = 0; r < rows; ++r) {
       f32x4 acc0 = (f32x4){b0, b1, b0, b1}, acc1 = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -531,10 +508,9 @@ __global__ __launch_bounds__(NTH) void conv_tail_slide_kernel(
           yp[0] = v0; yp[1] = v1;
         }
       }
-      SLIDE_BARRIER();
+      WG_BARRIER();
     }
   }
-#undef SLIDE_BARRIER
 }
 
 }  // namespace

@@ -23,14 +23,9 @@
 //     the counted vmcnt in front of the row barrier covers exactly the newest
 //     plane; the plane stream runs across the units of a workgroup without a
 //     pipeline refill.
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int SW_WAVES = 8;
 constexpr int SW_NTH = SW_WAVES * 64;
@@ -43,17 +38,6 @@ struct SweepShape {
   int plane_cells, npieces, plane_bytes;
   int seg, segs0, tiles1, tiles2, n_units;
 };
-
-__device__ inline unsigned sw_pk2(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
-__device__ inline float sw_act(float v, float slope) { return v > 0.f ? v : slope * v; }
-__device__ inline float sw_affine2(float v, float sc, float sh) {
-  float t = v * sc;
-  asm volatile("" : "+v"(t));
-  return t + sh;
-}
 
 template <int NSET>
 __global__ __launch_bounds__(SW_NTH) void conv_tail_sweep_kernel(
@@ -144,17 +128,16 @@ __global__ __launch_bounds__(SW_NTH) void conv_tail_sweep_kernel(
   // everything but the newest plane's pieces of this wave has landed
   auto wait_but_newest = [&](bool newest_in_flight) __attribute__((always_inline)) {
     switch (newest_in_flight ? my_np : 0) {
-      case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-      case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-      case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-      case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-      case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-      case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-      case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-      default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+      case 1: WAIT_VM(1); break;
+      case 2: WAIT_VM(2); break;
+      case 3: WAIT_VM(3); break;
+      case 4: WAIT_VM(4); break;
+      case 5: WAIT_VM(5); break;
+      case 6: WAIT_VM(6); break;
+      case 7: WAIT_VM(7); break;
+      default: WAIT_VM(0); break;
     }
   };
-#define SWEEP_BARRIER() asm volatile("s_barrier" ::: "memory")
 
   if (iu >= u_end) return;
   issue_setup();
@@ -178,15 +161,15 @@ __global__ __launch_bounds__(SW_NTH) void conv_tail_sweep_kernel(
       if (c >= 0 && c <= 2) {
         const float* wp = wl + (ab * 3 + c) * 8 * 2 + co;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = sw_pk2(wp[(2 * e) * 2], wp[(2 * e + 1) * 2]);
+        for (int e = 0; e < 4; ++e) u[e] = pk2(wp[(2 * e) * 2], wp[(2 * e + 1) * 2]);
       }
       uint4 uv = make_uint4(u[0], u[1], u[2], u[3]);
       wf[f] = __builtin_bit_cast(bf16x8, uv);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    WAIT_LGKM0();
   }
   wait_but_newest(second);
-  SWEEP_BARRIER();
+  WG_BARRIER();
 
   // rows q - 2 / q - 1 / q of the plane being read: R0 / R1 / R2
   f32x4 R0[NSET][2], R1[NSET][2], R2[NSET][2];
@@ -204,11 +187,11 @@ __global__ __launch_bounds__(SW_NTH) void conv_tail_sweep_kernel(
       if (row1[j] >= 0 && oo1 < g.O[1] && oo2 < g.O[2]) {
         float* yp = y + ((((size_t)pn * g.O[0] + po0) * g.O[1] + oo1) * g.O[2] + oo2) * 2;
         const f32x4 t = R0[j][0] + R0[j][1];
-        float v0 = sw_act(t[0], slope), v1 = sw_act(t[1], slope),
-              v2 = sw_act(t[2], slope), v3 = sw_act(t[3], slope);
+        float v0 = act_sel(t[0], slope), v1 = act_sel(t[1], slope),
+              v2 = act_sel(t[2], slope), v3 = act_sel(t[3], slope);
         if (aff) {
-          v0 = sw_affine2(v0, aff[0], aff[2]); v1 = sw_affine2(v1, aff[1], aff[3]);
-          v2 = sw_affine2(v2, aff[0], aff[2]); v3 = sw_affine2(v3, aff[1], aff[3]);
+          v0 = affine2(v0, aff[0], aff[2]); v1 = affine2(v1, aff[1], aff[3]);
+          v2 = affine2(v2, aff[0], aff[2]); v3 = affine2(v3, aff[1], aff[3]);
         }
         if (oo2 + 1 < g.O[2]) {
           __builtin_nontemporal_store((f32x4){v0, v1, v2, v3}, reinterpret_cast<f32x4*>(yp));
@@ -255,11 +238,10 @@ __global__ __launch_bounds__(SW_NTH) void conv_tail_sweep_kernel(
       if (q >= 2) { pend = true; pn = n; po0 = r0 + q - 2; po1 = o1; po2 = o2; }
       cslot = cslot == SW_NSLOT - 1 ? 0 : cslot + 1;
       wait_but_newest(newest);
-      SWEEP_BARRIER();
+      WG_BARRIER();
     }
   }
   if (pend) store_pending();
-#undef SWEEP_BARRIER
 }
 
 // plane shape and rows per unit for a launch: least time of the busiest

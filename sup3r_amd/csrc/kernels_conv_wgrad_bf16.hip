@@ -21,15 +21,9 @@
 // Partials per workgroup, reduced in fixed order (deterministic on every rank).
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int BT0 = 4, BT1 = 4, BT2 = 16;
 constexpr int BH0 = BT0 + 2, BH1 = BT1 + 2, BH2 = BT2 + 2;
@@ -40,11 +34,6 @@ constexpr int BCT = 32;                         // cout tile per workgroup
 constexpr int XS_BYTES = BHP * 128;             // 82,944
 constexpr int DS_BYTES = BNP * 64;              // 16,384
 constexpr size_t BF_LDS = (size_t)XS_BYTES + DS_BYTES;
-
-__device__ __forceinline__ unsigned pk2(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
 
 // 32-B segment swizzle of a halo cell: cells of equal parity among the 8 cells
 // one half-wave transpose read touches ({t..t+3} U {t+8..t+11}) get distinct keys
@@ -310,11 +299,11 @@ __global__ __launch_bounds__(WS_NT) void conv3_wgrad_bf16_ws_kernel(
       }
     };
     if (n_items > 0) load_item(0, smem);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the DMA landed before the hand-over
+    WAIT_VM(0);     // the DMA landed before the hand-over
     __syncthreads();
     for (int it = 0; it < n_items; ++it) {
       if (it + 1 < n_items) load_item(it + 1, smem + ((it + 1) & 1) * WBUF);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      WAIT_VM(0);
       __syncthreads();
     }
     return;
@@ -604,7 +593,6 @@ int bf_grid(const s3_ctx* ctx, const ConvGeom& g, int* n_tiles_out, int* t0,
   if (grid > n_tiles) grid = n_tiles;
   return grid;
 }
-
 
 // ===========================================================================
 // General variant for the discriminator convs: C_in = 32 (CIB = 2 blocks of 16)
@@ -1000,7 +988,6 @@ int bf_gen_launch(s3_ctx* ctx, const ConvGeom& g, const float* x, const float* d
   if (rg > 4096) rg = 4096;
   return launch_wgrad_bf16_reduce(ctx, partial, grid, wsize, dw, accumulate, rg);
 }
-
 
 // ===========================================================================
 // 2-D convs (spatial models: k = 3 x 3 x 1 on (N, s1, s2, 1, C)): same scheme

@@ -16,19 +16,9 @@
 // fixed order.
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pk2(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
 
 constexpr int C2_WAVES = 4;
 
@@ -107,7 +97,6 @@ __global__ __launch_bounds__(C2_WAVES * 64) void conv_wgrad_c2_kernel(
       // spot — waves sat in s_waitcnt 65 % of the time (profiles/r03/
       // pmc_train_start.txt) — here the NEXT step's 18 registers of loads are
       // in flight while this step goes through LDS and the MFMAs.
-      typedef short s16x4 __attribute__((ext_vector_type(4)));
       const int r = lane >> 1, hf = lane & 1;
       uint4 q0, q1;
       float2 c5[5];
@@ -297,7 +286,6 @@ __global__ __launch_bounds__(C2_WAVES * 64) void conv_wgrad_c2_kernel(
           __builtin_amdgcn_wave_barrier();
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-        typedef short s16x4 __attribute__((ext_vector_type(4)));
         const char* wb = dst + wave * 2048;
         s16x4 lh[2];
 #pragma unroll
@@ -529,8 +517,6 @@ int launch_conv_wgrad_c2(s3_ctx* ctx, const ConvGeom& g, const float* x, const f
 // through LDS at the end; one partial per workgroup.
 namespace {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TW0 = 4, TW1 = 8, TW2 = 32;
 constexpr int TG0 = TW0 + 2, TG1 = TW1 + 2, TG2 = TW2 + 2;
 constexpr int TWP = TG0 * TG1 * TG2;            // 2040 halo cells of 16 B
@@ -719,7 +705,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_tail_kernel(
   }
 }
 
-
 // ===========================================================================
 // Plane-sweep form of the tail conv's weight gradient (round 6; C_in = 8 bf16 cells,
 // C_out = 2, reflect padding): the same matrix product per halo row as
@@ -846,6 +831,7 @@ __global__ __launch_bounds__(WS_NTH) void conv_wgrad_tail_sweep_kernel(
       for (int k = 0; k < WS_DPT; ++k) {
         if (k >= my_nd || !dact[k]) continue;
         bf16x8 rv = ws_lds_b128(raw + k * (WS_WAVES * 1024));
+        // (not WAIT_LGKM0(): the "+v" operand pins the use of rv behind the wait)
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rv) :: "memory");
         float4 v = __builtin_bit_cast(float4, rv);
         if (!(o1 + drow[k] < O1 && o2 + dt[k] < O2)) v = make_float4(0.f, 0.f, 0.f, 0.f);   // (O2 is even)
@@ -911,20 +897,19 @@ __global__ __launch_bounds__(WS_NTH) void conv_wgrad_tail_sweep_kernel(
     // everything but the newest item's pieces of this wave has landed
     auto wait_but_newest = [&](bool newest_in_flight) __attribute__((always_inline)) {
       switch (newest_in_flight ? my_np + my_nd : 0) {
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+        case 1: WAIT_VM(1); break;
+        case 2: WAIT_VM(2); break;
+        case 3: WAIT_VM(3); break;
+        case 4: WAIT_VM(4); break;
+        case 5: WAIT_VM(5); break;
+        case 6: WAIT_VM(6); break;
+        case 7: WAIT_VM(7); break;
+        case 8: WAIT_VM(8); break;
+        case 9: WAIT_VM(9); break;
+        case 10: WAIT_VM(10); break;
+        default: WAIT_VM(0); break;
       }
     };
-#define WSW_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     // ---- prologue: items 0 and 1 in flight, dPre row 0 of the first unit -> slot 0
     issue_setup();
@@ -936,7 +921,7 @@ __global__ __launch_bounds__(WS_NTH) void conv_wgrad_tail_sweep_kernel(
       unit_org(u_first, n, r0, o1, o2);
       dpre_convert(0, 0, o1, o2);
     }
-    WSW_BARRIER();
+    WG_BARRIER_LDS();
 
     int cslot = 0, dbase = 0;
     for (int u = u_first; u < u_end; u += u_step) {
@@ -975,6 +960,7 @@ __global__ __launch_bounds__(WS_NTH) void conv_wgrad_tail_sweep_kernel(
             bfr[nb] = ws_lds_b128(ba);
           }
           s16x4 l0 = lo0, g0 = hi0, l1 = lo1, g1 = hi1;
+          // (not WAIT_LGKM0(): the "+v" operands pin the fragments behind the wait)
           asm volatile("s_waitcnt lgkmcnt(0)"
                        : "+v"(l0), "+v"(g0), "+v"(l1), "+v"(g1), "+v"(bfr[0]), "+v"(bfr[1]) :: "memory");
           const bf16x8 afr0 = __builtin_shufflevector(l0, g0, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -994,11 +980,10 @@ __global__ __launch_bounds__(WS_NTH) void conv_wgrad_tail_sweep_kernel(
         if (qq + 1 < rows) dpre_convert(nslot, (dbase + qq + 1) & 3, o1, o2);
         else if (qq == rows + 1 && more) dpre_convert(nslot, (dbase + rows) & 3, o12, o22);
         cslot = nslot;
-        WSW_BARRIER();
+        WG_BARRIER_LDS();
       }
       dbase = (dbase + rows) & 3;
     }
-#undef WSW_BARRIER
   }
 
   // ---- sum the 8 waves: red[wave][cp][nb][row m 16][column 16]

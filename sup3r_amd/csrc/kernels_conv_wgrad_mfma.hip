@@ -16,11 +16,9 @@
 // deterministic (identical on every rank).
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WT0 = 2, WT1 = 4, WT2 = 16;
 constexpr int WH0 = WT0 + 2, WH1 = WT1 + 2, WH2 = WT2 + 2;

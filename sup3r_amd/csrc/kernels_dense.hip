@@ -6,17 +6,11 @@
 // per pass), and K is split over the grid with a deterministic two-stage sum.
 #include <cstdlib>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
 
 constexpr int NB = 8;
-
-__device__ inline float act_f(float v, int act, float alpha) {
-  if (act == S3_ACT_RELU) return v > 0.f ? v : 0.f;
-  if (act == S3_ACT_LEAKY) return v > 0.f ? v : alpha * v;
-  return v;
-}
 
 // partial[kslab][n][u]
 __global__ __launch_bounds__(256) void dense_fwd_stage1(
@@ -72,7 +66,7 @@ __global__ void dense_fwd_stage2(const float* __restrict__ partial,
     for (; s < n_slabs; ++s) t0 += partial[(int64_t)s * total + idx];
     float t = (t0 + t1) + (t2 + t3);
     if (bias) t += bias[idx % cout];
-    y[idx] = act_f(t, act, alpha);
+    y[idx] = act_f_branch(t, act, alpha);
   }
 }
 

@@ -4,6 +4,7 @@
 // gradient, with the variants launch_fold chooses between.  One-pass streaming
 // kernels: coalesced 16-B accesses where the channel count allows.
 #include "kernels_support.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -233,22 +234,12 @@ __global__ void gather_bwd_pad4_kernel(const float* __restrict__ dout,
       acc.x += y.x; acc.y += y.y; acc.z += y.z; acc.w += y.w;
     }
     if constexpr (OUT16) {
-      typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-      typedef float f2 __attribute__((ext_vector_type(2)));
-      const f2 lo2 = {acc.x, acc.y}, hi2 = {acc.z, acc.w};
       *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(din) + idx * 4) =
-          make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(lo2, bf2)),
-                     __builtin_bit_cast(unsigned, __builtin_convertvector(hi2, bf2)));
+          make_uint2(pk2(acc.x, acc.y), pk2(acc.z, acc.w));
     } else {
       *reinterpret_cast<float4*>(din + idx * 4) = acc;
-      if constexpr (SIDE16) {
-        typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        const f2 lo2 = {acc.x, acc.y}, hi2 = {acc.z, acc.w};
-        *reinterpret_cast<uint2*>(side16 + idx * 4) =
-            make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(lo2, bf2)),
-                       __builtin_bit_cast(unsigned, __builtin_convertvector(hi2, bf2)));
-      }
+      if constexpr (SIDE16)
+        *reinterpret_cast<uint2*>(side16 + idx * 4) = make_uint2(pk2(acc.x, acc.y), pk2(acc.z, acc.w));
     }
     bs.x += acc.x; bs.y += acc.y; bs.z += acc.z; bs.w += acc.w;
   }
@@ -336,13 +327,7 @@ __global__ void fold16x8_kernel(const unsigned short* __restrict__ frame, float*
       acc[0] += y0.x; acc[1] += y0.y; acc[2] += y0.z; acc[3] += y0.w;
       acc[4] += y1.x; acc[5] += y1.y; acc[6] += y1.z; acc[7] += y1.w;
     }
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    auto pk = [](float lo, float hi) {
-      const f2 v = {lo, hi};
-      return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf2));
-    };
-    const uint4 o16 = make_uint4(pk(acc[0], acc[1]), pk(acc[2], acc[3]), pk(acc[4], acc[5]), pk(acc[6], acc[7]));
+    const uint4 o16 = make_uint4(pk2(acc[0], acc[1]), pk2(acc[2], acc[3]), pk2(acc[4], acc[5]), pk2(acc[6], acc[7]));
     if constexpr (OUT16) {
       *reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(din) + idx * 8) = o16;
     } else {

@@ -26,14 +26,9 @@
 #include <cstdlib>
 #include <vector>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 hbf16x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int FNW = 8;            // waves per workgroup
 constexpr int FNT = FNW * 64;
@@ -56,13 +51,6 @@ struct FL {
   int cin;         // input channels
   int w_off;       // float offset of the canonical filter in the weight buffer
 };
-
-__device__ __forceinline__ unsigned pk2(float a, float b) {
-  hf32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hbf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float hi_f(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
 
 // canonical fp32 w[tap 9][cin][cout] -> bf16 [nf][tap][ks][row 16][k 32]
 __global__ void fused2d_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ img,
@@ -194,7 +182,7 @@ __device__ __forceinline__ void run_layer(const FL& L, const char* __restrict__ 
       const unsigned daddr = (unsigned)(dcell * 128 + (((cc0 >> 3) ^ (dcell & 7)) << 4) + (cc0 & 7) * 2);
       if (L.res >= 0) {
         const uint2 rr = *reinterpret_cast<const uint2*>(smem + L.res + daddr);
-        v[0] += lo_f(rr.x); v[1] += hi_f(rr.x); v[2] += lo_f(rr.y); v[3] += hi_f(rr.y);
+        v[0] += bf_lo(rr.x); v[1] += bf_hi(rr.x); v[2] += bf_lo(rr.y); v[3] += bf_hi(rr.y);
       }
       *reinterpret_cast<uint2*>(smem + L.dst + daddr) = make_uint2(pk2(v[0], v[1]), pk2(v[2], v[3]));
     }

@@ -15,7 +15,7 @@
 // range reduced in fixed order, bitonic sort, tree reductions, no atomics.
 #include <cstdint>
 
-#include "common.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -24,19 +24,6 @@ constexpr int SWC = 16;    // (observation, feature) columns per pass
 constexpr int SWT = 256;   // positions per LDS tile
 constexpr int SWROW = 2 * SWC + 1;  // partial row: 16 + 16 sums, |dir|^2
 constexpr int SWPC = 512;  // projections per LDS chunk (backward)
-
-__device__ __forceinline__ void philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                        uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // the four standard normals of projection p at positions 4 l4 .. 4 l4 + 3
 __device__ __forceinline__ void sw_normals(uint64_t seed, uint32_t p, uint64_t l4, float z[4]) {

@@ -2,16 +2,11 @@
 // mask pass of a conv (activation adjoint + depth-to-space store permutation,
 // optionally with a bf16 copy and riding channel sums), residual adds, fill.
 #include "kernels_support.h"
+#include "wave_prims.h"
 
 namespace {
 
 // ------------------------------------------------------------- elementwise
-__device__ inline float act_f(float v, int act, float alpha) {
-  // one select for every kind (slope 1 = identity, 0 = ReLU, alpha = Leaky):
-  // testing the kind per element compiles to two scalar branches per value
-  const float s = act == S3_ACT_LEAKY ? alpha : (act == S3_ACT_RELU ? 0.f : 1.f);
-  return v > 0.f ? v : s * v;
-}
 __device__ inline float act_d(float y, int act, float alpha) {
   if (act == S3_ACT_RELU) return y > 0.f ? 1.f : 0.f;
   if (act == S3_ACT_LEAKY) return y > 0.f ? 1.f : alpha;
@@ -133,12 +128,7 @@ __global__ void conv_epilogue_bwd_d2s4_kernel(const void* __restrict__ y, const 
     if (dpre) dpre[idx] = d;
     bs.x += d.x; bs.y += d.y; bs.z += d.z; bs.w += d.w;
     if constexpr (D16) {   // bf16 copy for the MFMA gradient kernels
-      typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-      typedef float f2 __attribute__((ext_vector_type(2)));
-      const f2 lo2 = {d.x, d.y}, hi2 = {d.z, d.w};
-      reinterpret_cast<uint2*>(d16)[idx] =
-          make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(lo2, bf2)),
-                     __builtin_bit_cast(unsigned, __builtin_convertvector(hi2, bf2)));
+      reinterpret_cast<uint2*>(d16)[idx] = make_uint2(pk2(d.x, d.y), pk2(d.z, d.w));
     }
   }
   if (bsum) {
@@ -183,12 +173,7 @@ __global__ void conv_epilogue_bwd4_kernel(const void* __restrict__ y, const floa
     if (dpre) dpre[i] = d;
     bs.x += d.x; bs.y += d.y; bs.z += d.z; bs.w += d.w;
     if (d16) {   // bf16 copy for the MFMA gradient kernels (see gather_bwd_pad4_kernel)
-      typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-      typedef float f2 __attribute__((ext_vector_type(2)));
-      const f2 lo2 = {d.x, d.y}, hi2 = {d.z, d.w};
-      reinterpret_cast<uint2*>(d16)[i] =
-          make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(lo2, bf2)),
-                     __builtin_bit_cast(unsigned, __builtin_convertvector(hi2, bf2)));
+      reinterpret_cast<uint2*>(d16)[i] = make_uint2(pk2(d.x, d.y), pk2(d.z, d.w));
     }
   }
   if (bsum) {
@@ -221,13 +206,7 @@ __global__ void add_kernel(const float* __restrict__ a,
 // the convs on either side keep their bf16 kernels)
 __global__ void add16_kernel(const uint4* __restrict__ a, const uint4* __restrict__ b, uint4* __restrict__ y,
                              int64_t n8) {
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  auto add2 = [](unsigned u, unsigned v) {
-    const f2 s = {__uint_as_float(u << 16) + __uint_as_float(v << 16),
-                  __uint_as_float(u & 0xFFFF0000u) + __uint_as_float(v & 0xFFFF0000u)};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(s, bf2));
-  };
+  auto add2 = [](unsigned u, unsigned v) { return pk2(bf_lo(u) + bf_lo(v), bf_hi(u) + bf_hi(v)); };
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
     const uint4 p = a[i], q = b[i];
