@@ -841,6 +841,101 @@ int s3_bias_correct(s3_ctx* ctx, const float* x, int n, int s1, int s2, int t, i
                     const double* weights, const double* mean_host, const double* std_host,
                     int stats_fp32, float* out, int32_t* nonfinite);
 
+/* ---- computing bias-correction factors on the device -----------------------
+ * the per-pixel work of sup3r/bias/bias_calc.py (LinearCorrection and its
+ * monthly / scalar kin), qdm.py (QuantileDeltaMappingCorrection) and presrat.py:
+ * the tables that the correction above applies.  Every series is fp32 (P, T),
+ * pixel-major (P = the low-res grid, flattened).  Sums are fp64 and rounded to
+ * fp32 once; each output value comes from one thread or from one workgroup's
+ * fixed reduction tree; no float atomics.  Index lists come twice: a host copy
+ * that is range-checked here before anything is launched, and the device copy
+ * that the kernel reads.  All five are asynchronous on the context's stream.
+ *
+ * s3_bc_base_series: base (T, n_sites) -> out[p, day_offset + d], d < n_days:
+ *   per step the mean over the pixel's sites (CSR site_ptr (P + 1) / site_idx;
+ *   S3_BCC_NANSKIP: np.nanmean, a step whose sites are all NaN is NaN;
+ *   otherwise a plain mean), then the reduction over the day's steps (CSR
+ *   day_ptr (n_days + 1) / step_idx, any order of steps).  The reductions skip
+ *   NaN steps like pandas' groupby: avg / max / min of a day without a valid
+ *   step are NaN, its sum is 0; S3_BCC_NONE wants one step per output step.
+ *   S3_BCC_CS_RATIO (avg only): daily sum of base over daily sum of cs_ghi,
+ *   0 / 1 where the latter is 0 (base.py:745-749).  S3_BCC_ROUND: np.around(.,
+ *   decimals) in fp32, round-half-even at the scaled value.  A pixel without
+ *   sites gets NaN.  D_total is the row length of out: one launch per base
+ *   file writes its days at day_offset.
+ * s3_bc_moments: per (pixel, group) count / np.nanmean / np.nanstd (mean,
+ *   then the mean of the squared deviations, ddof = 0) of the steps with
+ *   group[t] == g; group[t] = -1 belongs to none; NT <= S3_BCC_MAX_GROUPS.  A
+ *   group without a non-NaN member gives count 0 and NaN.  Outputs (P, NT).
+ * s3_bc_window_quantiles: per (pixel, window) the members (CSR win_ptr (W + 1)
+ *   / member, indices into the series) are sorted in LDS on an integer key in
+ *   float order (-0 < +0, NaN last) and out (P, W, Q) receives np.quantile at
+ *   np.linspace(0, 1, Q): order statistics interpolated linearly in fp64 at
+ *   (n - 1) q.  q = 0 and q = 1 are the minimum and maximum exactly; Q = 1
+ *   gives the minimum.  A window that is empty or holds a NaN gives a NaN row.
+ * s3_bc_match_zero_rate (base.py:557-599): in place on bias (P, T): the
+ *   pixel's sorted series, np.interp of the share of exact zeros of its base
+ *   row (P, D) into np.linspace(0, 1, T) in fp64 (written to min_value (P),
+ *   optional), and everything below that set to 0.  nonfinite: one int32 the
+ *   number of non-finite bias values is added to; such a pixel is left as it
+ *   is (the reference's sorted() on NaN is undefined).
+ * s3_bc_presrat (presrat.py:96-360), per pixel and in the reference's order:
+ *   the QDM-corrected future series (corrected (P, Tf), written always: step t
+ *   is mapped with the rows of window last_window[t], the last window that
+ *   holds it, and stays NaN for -1; the mapping is that of s3_bias_correct
+ *   with delta_denom_min = zero_rate_threshold when relative, on the tables
+ *   (P, W, Q) given); zero_rate (P) = the share of finite base values <=
+ *   threshold (compared in fp32, as numpy does); tau = the order statistic
+ *   min(round(rate Tb), Tb - 1) of the bias series, round half to even on the
+ *   fp64 product; z_fg = #(fut < tau) / Tf; tau_fut (P) = the order statistic
+ *   round(z_fg Tf) of the corrected series, NaN sorted last; k_factor (P, W)
+ *   from the four plain (not NaN-skipping) window means floored at the
+ *   threshold, in fp64.  tau and z_fg (P) are optional outputs.  The window
+ *   lists come as three pointers each: base, bias, future.  status
+ *   (S3_BCC_PR_STATUS_WORDS int32, zeroed here): non-finite bias values,
+ *   non-finite future values, pixels whose round(z_fg Tf) = Tf (the
+ *   reference's IndexError; their tau_fut is NaN).  Q >= 2.
+ *
+ * S3_EINVAL, before anything is launched: a sorted segment longer than
+ * S3_BCC_MAX_SORT (its keys fill 128 KiB of the CU's 160 KiB of LDS), a site,
+ * step, member or group index out of range, lists that do not ascend, days
+ * that leave out, Q < 1, NT outside 1 .. 12, 2^31 or more elements. */
+#define S3_BCC_MAX_SORT 32768
+#define S3_BCC_MAX_GROUPS 12
+#define S3_BCC_AVG 0
+#define S3_BCC_MAX 1
+#define S3_BCC_MIN 2
+#define S3_BCC_SUM 3
+#define S3_BCC_NONE 4
+#define S3_BCC_NANSKIP 1u
+#define S3_BCC_CS_RATIO 2u
+#define S3_BCC_ROUND 4u
+#define S3_BCC_PR_STATUS_WORDS 3
+#define S3_BCC_PR_BIAS_NONFINITE 0
+#define S3_BCC_PR_FUT_NONFINITE 1
+#define S3_BCC_PR_INDEX 2
+int s3_bc_base_series(s3_ctx* ctx, const float* base, const float* cs_ghi, int64_t T, int64_t n_sites,
+                      int P, const int32_t* site_ptr_host, const int32_t* site_idx_host,
+                      const int32_t* site_ptr, const int32_t* site_idx, int n_days,
+                      const int32_t* day_ptr_host, const int32_t* step_idx_host,
+                      const int32_t* day_ptr, const int32_t* step_idx, int reduction, uint32_t flags,
+                      int decimals, int64_t D_total, int64_t day_offset, float* out);
+int s3_bc_moments(s3_ctx* ctx, const float* series, int P, int64_t T, const int32_t* group_host,
+                  const int32_t* group, int NT, int32_t* count, float* mean, float* sd);
+int s3_bc_window_quantiles(s3_ctx* ctx, const float* series, int P, int64_t T, int W,
+                           const int32_t* win_ptr_host, const int32_t* member_host,
+                           const int32_t* win_ptr, const int32_t* member, int Q, float* out);
+int s3_bc_match_zero_rate(s3_ctx* ctx, const float* base, int64_t D, float* bias, int P, int64_t T,
+                          double* min_value, int32_t* nonfinite);
+int s3_bc_presrat(s3_ctx* ctx, const float* base, int64_t D, const float* bias, int64_t Tb,
+                  const float* fut, int64_t Tf, int P, int W, int Q, const float* base_params,
+                  const float* bias_params, const float* fut_params, int relative,
+                  double zero_rate_threshold, const int32_t* last_window_host,
+                  const int32_t* last_window, const int32_t* const* win_ptr_host,
+                  const int32_t* const* member_host, const int32_t* const* win_ptr,
+                  const int32_t* const* member, float* corrected, float* zero_rate, float* tau,
+                  float* z_fg, float* tau_fut, float* k_factor, int32_t* status);
+
 /* ---- non-neural downscalers on the device ------------
  * replaces the host scipy / Pillow of the reference's LinearInterp and
  * SurfaceSpatialMetModel (sup3r/models/linear.py, sup3r/models/surface.py):

@@ -26,6 +26,8 @@ from .batch_queue import (DeviceBatchHandler, DeviceBatchQueue,  # noqa: E402,F4
 from .bias import (BiasParams, DeviceBiasCorrection,  # noqa: E402,F401
                    global_linear_bc, local_linear_bc, local_presrat_bc,
                    local_qdm_bc, monthly_local_linear_bc)
+from . import bias_calc as _bias_calc  # noqa: E402
+from .bias_calc import *  # noqa: E402,F401,F403
 from . import batch_queue_conditional as _cond  # noqa: E402
 from .batch_queue_conditional import *  # noqa: E402,F401,F403
 from . import samplers as _samplers  # noqa: E402
@@ -41,4 +43,4 @@ __all__ = ['Sup3rGan', 'Sup3rCondMom', 'Sup3rGanDC', 'SolarCC', 'Sup3rGanWithObs
            'MultiStepSurfaceMetGan', 'SolarMultiStepGan', 'LinearInterp', 'SurfaceSpatialMetModel', 'ForwardPass', 'ChunkPathOptions',
            'ChunkSlicer', 'BiasParams', 'DeviceBiasCorrection', 'global_linear_bc', 'local_linear_bc',
            'monthly_local_linear_bc', 'local_qdm_bc', 'local_presrat_bc', 'DeviceBatchQueue', 'DeviceBatchHandler', 'DsetTuple',
-           *_cond.__all__, *_samplers.__all__, *_samplers_cc.__all__, *_dc.__all__, *_dual.__all__, '__version__']
+           *_bias_calc.__all__, *_cond.__all__, *_samplers.__all__, *_samplers_cc.__all__, *_dc.__all__, *_dual.__all__, '__version__']

@@ -43,6 +43,8 @@ EXPORTS = [
     's3_specmap',
     's3_copy_channels', 's3_affine_channels', 's3_fill', 's3_copy_block',
     's3_coarsen', 's3_gaussian_smooth', 's3_condmom_target', 's3_bias_correct', 's3_chunk_stats',
+    's3_bc_base_series', 's3_bc_moments', 's3_bc_window_quantiles',
+    's3_bc_match_zero_rate', 's3_bc_presrat',
     's3_sample_gather', 's3_cc_night_mask', 's3_cc_window_gather',
     's3_nn_fill',
     's3_st_interp', 's3_resize2d', 's3_surface_downscale',
@@ -255,6 +257,17 @@ def lib():
                                   C.POINTER(i32), vp, vp, vp,
                                   C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), i32, vp, vp]),
+        's3_bc_base_series': (i32, [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp,
+                                    i32, vp, vp, vp, vp, i32, C.c_uint32, i32,
+                                    i64, i64, vp]),
+        's3_bc_moments': (i32, [vp, vp, i32, i64, vp, vp, i32, vp, vp, vp]),
+        's3_bc_window_quantiles': (i32, [vp, vp, i32, i64, i32, vp, vp, vp,
+                                         vp, i32, vp]),
+        's3_bc_match_zero_rate': (i32, [vp, vp, i64, vp, i32, i64, vp, vp]),
+        's3_bc_presrat': (i32, [vp, vp, i64, vp, i64, vp, i64, i32, i32, i32,
+                                vp, vp, vp, i32, C.c_double, vp, vp,
+                                C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                C.POINTER(vp), vp, vp, vp, vp, vp, vp, vp]),
         's3_st_interp': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp,
                                vp]),
         's3_resize2d': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp,
@@ -340,6 +353,11 @@ BC_NONE, BC_LINEAR, BC_QDM = 0, 1, 2
 (BC_MONTH, BC_WEIGHTS, BC_SCALAR_RANGE, BC_ADDER_RANGE, BC_OUT_RANGE,
  BC_PER_CHUNK, BC_RELATIVE, BC_NO_TREND, BC_DENOM_ZERO, BC_DENOM_MIN,
  BC_DELTA_RANGE, BC_PRESRAT, BC_GLOBAL) = (1 << i for i in range(13))
+# s3_bc_*: sort limit, daily reductions, flags (include/sup3r_hip.h)
+BCC_MAX_SORT, BCC_MAX_GROUPS = 32768, 12
+BCC_AVG, BCC_MAX, BCC_MIN, BCC_SUM, BCC_NONE = range(5)
+BCC_NANSKIP, BCC_CS_RATIO, BCC_ROUND = 1, 2, 4
+BCC_PR_BIAS_NONFINITE, BCC_PR_FUT_NONFINITE, BCC_PR_INDEX = 0, 1, 2
 
 
 def last_error(ctx):

@@ -32,9 +32,12 @@ reference's dataset names (``{feature}_scalar``, ``{feature}_adder``,
 optional ``latitude`` / ``longitude``) and attributes (``time_window_center``,
 ``dist``, ``sampling``, ``log_base``, ``zero_rate_threshold``).
 
-Not here: computing the factors (sup3r/bias/bias_calc.py, qdm.py, presrat.py),
-parametric ``dist`` and the log samplings (defined inside ``rex``), and the
-resident-domain executor (``ForwardPass.run_batched`` / ``upload_domain``).
+The factors themselves are computed by ``sup3r_amd.bias_calc``, whose ``.npz``
+output is read here unchanged.
+
+Not here: parametric ``dist`` and the log samplings (defined inside ``rex``),
+and the resident-domain executor (``ForwardPass.run_batched`` /
+``upload_domain``).
 The empirical quantile mapping itself lives in ``rex``
 (``rex.utilities.bc_utils.QuantileDeltaMapping``), which is not available
 where this project is built: it is restated from ``numpy.interp`` and Cannon
