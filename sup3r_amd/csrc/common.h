@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/sup3r_hip.h"
+#include "launch_shape.h"
 
 
 // ---- plan / context options -------------------------------------------------
@@ -171,11 +172,12 @@ struct s3_ctx {
   struct PendingBias { const float* partial = nullptr; int nblk = 0, c = 0; float* db = nullptr; int accumulate = 0; } pend_bias;
 };
 
-// One-time per-DEVICE setup of a launch function (hipFuncSetAttribute's dynamic-LDS
-// limit is a property of the function ON A DEVICE): `static S3DeviceOnce o; if
-// (!o.done(ctx->device)) { std::lock_guard<std::mutex> lk(o.m); ...; o.mark(ctx->device); }`
-// — lock-free once set; two threads racing on the first call both run the (idempotent)
-// setup, one after the other.
+// One-time per-DEVICE setup of a launch function (the dynamic-LDS limit is a
+// property of the function ON A DEVICE).  The flag stays with its launcher,
+//   static S3DeviceOnce once;
+//   if (int rc = s3_lds_optin(ctx, once, kernel_a, LDS_A, kernel_b, LDS_B)) return rc;
+// (s3_lds_optin below) — lock-free once set; two threads racing on the first
+// call both run the (idempotent) setup, one after the other.
 struct S3DeviceOnce {
   std::atomic<uint64_t> mask{0};
   std::mutex m;
@@ -197,6 +199,27 @@ struct S3DeviceOnce {
     (ctx)->err = (msg);         \
     return (code);              \
   } while (0)
+
+// The dynamic-LDS opt-in of a launcher's kernels, once per device: (kernel,
+// bytes) pairs.  S3_OK at once where `once` has the device; else every pair gets
+// hipFuncAttributeMaxDynamicSharedMemorySize under the flag's mutex and the
+// device is marked.  A HIP error: ctx->err and S3_EHIP, the device unmarked.
+// (s3_lds_set alone: a limit that follows the call's arguments, set every time)
+inline int s3_lds_set(s3_ctx*) { return S3_OK; }
+template <class K, class B, class... Rest>
+int s3_lds_set(s3_ctx* ctx, K* kernel, B bytes, Rest... rest) {
+  S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return s3_lds_set(ctx, rest...);
+}
+template <class... Pairs>
+inline int s3_lds_optin(s3_ctx* ctx, S3DeviceOnce& once, Pairs... pairs) {
+  if (once.done(ctx->device)) return S3_OK;
+  std::lock_guard<std::mutex> lk(once.m);
+  const int rc = s3_lds_set(ctx, pairs...);
+  if (rc == S3_OK) once.mark(ctx->device);
+  return rc;
+}
 
 // geometry of one fused convolution, passed by value to kernels
 struct ConvGeom {

@@ -556,12 +556,8 @@ int launch_io(s3_ctx* ctx, const ConvGeom& g, const void* x, const void* wpk,
   using T = Tile<TS0, TS1, NW, KA>;
   const size_t lds = PREC == S3_PREC_F32 ? T::lds_f32 : T::lds_bf16;
   auto kern = conv3_mfma_kernel<PREC, TS0, TS1, NW, IN16, OUT16, NFV, KA, GEN>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  static S3DeviceOnce attr_set;
+  if (int rc = s3_lds_optin(ctx, attr_set, kern, lds)) return rc;
   const int tiles0 = (g.O[0] + TS0 - 1) / TS0, tiles1 = (g.O[1] + TS1 - 1) / TS1,
             tiles2 = (g.O[2] + TS2 - 1) / TS2;
   dim3 grid((unsigned)(g.N * tiles0 * tiles1 * tiles2), (unsigned)((g.Cout + CT - 1) / CT));

@@ -468,16 +468,10 @@ bool csr_ok(const int32_t* ptr, int n, const int32_t* idx, int64_t limit) {
 
 int allow_big_lds(s3_ctx* ctx) {
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(window_quantiles_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSort * 4));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(match_zero_rate_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSort * 4));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(presrat_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSort * 4));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            window_quantiles_kernel, kMaxSort * 4,
+                            match_zero_rate_kernel, kMaxSort * 4,
+                            presrat_kernel, kMaxSort * 4)) return rc;
   return S3_OK;
 }
 

@@ -33,7 +33,7 @@
 
 namespace {
 
-constexpr int kBlk = 256;
+constexpr int kBlk = kBlock;   // grid_for counts workgroups of this size
 constexpr int kTile = 2048;              // keys staged per workgroup (16 KiB)
 constexpr int kMaxAxis = S3_NN_FILL_MAX_AXIS;
 constexpr uint64_t kNone = ~0ull;
@@ -175,10 +175,7 @@ extern "C" int s3_nn_fill(s3_ctx* ctx, float* x, int n, int s1, int s2, int t, i
   g.dT = FastDiv(t); g.dS2 = FastDiv(s2); g.dS1 = FastDiv(s1);
   uint64_t* key = static_cast<uint64_t*>(work);
   uint32_t* bits = reinterpret_cast<uint32_t*>(x);
-  int64_t grid = (total + kBlk - 1) / kBlk;
-  const int64_t cap = (int64_t)ctx->num_cu * 8;
-  if (grid > cap) grid = cap;
-  hipLaunchKernelGGL(nn_fill_init_kernel, dim3((unsigned)grid), dim3(kBlk), 0, ctx->stream, g, bits, key, count);
+  hipLaunchKernelGGL(nn_fill_init_kernel, dim3(grid_for(total, ctx->num_cu)), dim3(kBlk), 0, ctx->stream, g, bits, key, count);
   S3_HIP(ctx, hipGetLastError());
   // the pass along t first (its lines lie along memory), then s2, s1, n;
   // an axis of extent 1 has nothing to look at
@@ -237,10 +234,7 @@ extern "C" int s3_cc_night_mask(s3_ctx* ctx, const float* data, int64_t S1, int6
     for (int m = 0; m < kMaxN; ++m)
       for (int a = 0; a < 3; ++a) g.org[m][a] = m < nl ? origins_host[(size_t)(m0 + m) * 3 + a] : 0;
     g.total = (uint32_t)((int64_t)nl * s1 * s2 * 24);
-    int64_t grid = ((int64_t)g.total + kBlk - 1) / kBlk;
-    const int64_t cap = (int64_t)ctx->num_cu * 8;
-    if (grid > cap) grid = cap;
-    hipLaunchKernelGGL(cc_night_mask_kernel, dim3((unsigned)grid), dim3(kBlk), 0, ctx->stream, g,
+    hipLaunchKernelGGL(cc_night_mask_kernel, dim3(grid_for(g.total, ctx->num_cu)), dim3(kBlk), 0, ctx->stream, g,
                        reinterpret_cast<const uint32_t*>(data), reinterpret_cast<unsigned*>(status));
     S3_HIP(ctx, hipGetLastError());
   }

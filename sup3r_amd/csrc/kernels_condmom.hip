@@ -19,7 +19,7 @@
 
 namespace {
 
-constexpr int kBlk = 256;
+constexpr int kBlk = kBlock;   // grid_for counts workgroups of this size
 constexpr int kMaxC = 32;
 
 // (the index arithmetic of a vector is six divisions by run-time constants:
@@ -221,15 +221,12 @@ extern "C" int s3_condmom_target(s3_ctx* ctx, const float* hr, const float* lr, 
                    (!(flags & S3_CM_MOM1) || c_m != c_hr || aligned16(mom1));
   // memory bound: at most 8 workgroups per CU, the rest by grid stride
   const int64_t items = vec ? (total + 3) / 4 : total;
-  int64_t grid = (items + kBlk - 1) / kBlk;
-  const int64_t cap = (int64_t)ctx->num_cu * 8;
-  if (grid > cap) grid = cap;
-  if (grid < 1) grid = 1;
+  const int grid = grid_for(items, ctx->num_cu);
   if (vec)
-    hipLaunchKernelGGL(condmom_target_vec_kernel, dim3((unsigned)grid), dim3(kBlk), 0, ctx->stream,
+    hipLaunchKernelGGL(condmom_target_vec_kernel, dim3(grid), dim3(kBlk), 0, ctx->stream,
                        g, hr, lr, mom1, out, mask);
   else
-    hipLaunchKernelGGL(condmom_target_scalar_kernel, dim3((unsigned)grid), dim3(kBlk), 0,
+    hipLaunchKernelGGL(condmom_target_scalar_kernel, dim3(grid), dim3(kBlk), 0,
                        ctx->stream, g, hr, lr, mom1, out, mask);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;

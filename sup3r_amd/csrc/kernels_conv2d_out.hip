@@ -276,12 +276,7 @@ int launch_conv2d_out(s3_ctx* ctx, const ConvGeom& g, int precision, const void*
 #define OUT_LAUNCH(X3_, NF_)                                                                                   \
   {                                                                                                            \
     static S3DeviceOnce once;                                                                                  \
-    if (!once.done(ctx->device)) {                                                                             \
-      std::lock_guard<std::mutex> lk(once.m);                                                                  \
-      S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_out_kernel<X3_, NF_>),              \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                \
-      once.mark(ctx->device);                                                                                  \
-    }                                                                                                          \
+    if (int rc = s3_lds_optin(ctx, once, conv2d_out_kernel<X3_, NF_>, 160 * 1024)) return rc;                  \
     hipLaunchKernelGGL((conv2d_out_kernel<X3_, NF_>), dim3((unsigned)grid), dim3(64 * OUT_WAVES), lds, ctx->stream, x, \
                        (const uint4*)image, bias, (float*)y, o);                                               \
   }

@@ -969,24 +969,14 @@ int launch_conv2d_ws_pack(s3_ctx* ctx, const ConvGeom& g, const float* w, void* 
 int launch_conv2d_ws(s3_ctx* ctx, const ConvGeom& g, const void* x, const void* image, const float* bias,
                      const void* res, void* y) {
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_ws_kernel<4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_ws_kernel<1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_ws_kernel<4, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_EXO));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_ws_kernel<4, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_ws_kernel<4, true, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_EXO));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_ws_pp_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_ws_pp_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            conv2d_ws_kernel<4>, W_LDS,
+                            conv2d_ws_kernel<1>, W_LDS,
+                            conv2d_ws_kernel<4, true>, W_LDS_EXO,
+                            conv2d_ws_kernel<4, false, true>, W_LDS,
+                            conv2d_ws_kernel<4, true, true>, W_LDS_EXO,
+                            conv2d_ws_pp_kernel<false>, W_LDS,
+                            conv2d_ws_pp_kernel<true>, W_LDS)) return rc;
   WsGeom w;
   w.N = g.N; w.H = g.D[0]; w.W = g.D[1];
   w.Cout = g.Cout; w.b = g.d2s < 1 ? 1 : g.d2s; w.cpo = g.Cout / (w.b * w.b);
@@ -1001,9 +991,7 @@ int launch_conv2d_ws(s3_ctx* ctx, const ConvGeom& g, const void* x, const void* 
   // at most one workgroup per CU over all output-channel tiles (each keeps ITS image; a
   // workgroup fills a CU's LDS, so one more than there are CUs would run after the others:
   // 25 channel tiles of the 64 -> 1600 conv x 11 = 275 workgroups was two rounds)
-  int gx = ctx->num_cu / n_ct;
-  if (gx > T) gx = T;
-  if (gx < 1) gx = 1;
+  const int gx = persistent_grid_min1(ctx->num_cu / n_ct, T);
   if (g.w_cin && !g.exo) S3_FAIL(ctx, S3_ESTATE, "conv2d_ws: the exogenous channel's field is not bound");
   if (g.res2 && (tail || w.b != 1)) S3_FAIL(ctx, S3_ESTATE, "conv2d_ws: a second skip operand needs the trunk form without depth-to-space");
   if (tail)
@@ -1013,9 +1001,7 @@ int launch_conv2d_ws(s3_ctx* ctx, const ConvGeom& g, const void* x, const void* 
   else if (!g.w_cin && !s3_opt_on(S3O_NO_WS_PP)) {
     // the ping-pong form: single-image tiles, two half-workgroups half a period apart
     const int T1 = g.N * w.tiles_r * w.tiles_c;
-    int gp = ctx->num_cu / n_ct;
-    if (gp > (T1 + 1) / 2) gp = (T1 + 1) / 2;
-    if (gp < 1) gp = 1;
+    const int gp = persistent_grid_min1(ctx->num_cu / n_ct, (T1 + 1) / 2);
     auto kern = res ? conv2d_ws_pp_kernel<true> : conv2d_ws_pp_kernel<false>;
     hipLaunchKernelGGL(kern, dim3(gp, n_ct), dim3(W_NT), W_LDS, ctx->stream, (const unsigned short*)x,
                        (const char*)image, bias, (const unsigned short*)res, (unsigned short*)y, w,

@@ -625,18 +625,11 @@ int launch_conv2d_ws_x3_pack(s3_ctx* ctx, const ConvGeom& g, const float* w, voi
 int launch_conv2d_ws_x3(s3_ctx* ctx, const ConvGeom& g, const void* x, const void* image, const float* bias,
                         const void* res, void* y) {
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_ws_x3_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_ws_x3_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_ws_x3_pp_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_ws_x3_pp_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            conv2d_ws_x3_kernel<false>, X_LDS,
+                            conv2d_ws_x3_kernel<true>, X_LDS,
+                            conv2d_ws_x3_pp_kernel<false>, X_LDS,
+                            conv2d_ws_x3_pp_kernel<true>, X_LDS)) return rc;
   X3Geom w;
   w.N = g.N; w.H = g.D[0]; w.W = g.D[1];
   w.Cout = g.Cout; w.b = g.d2s < 1 ? 1 : g.d2s; w.cpo = g.Cout / (w.b * w.b);
@@ -645,15 +638,11 @@ int launch_conv2d_ws_x3(s3_ctx* ctx, const ConvGeom& g, const void* x, const voi
   w.tiles_i = (g.N + XT_I - 1) / XT_I;
   w.tiles_r = (w.H + XT_R - 1) / XT_R; w.tiles_c = (w.W + XT_C - 1) / XT_C;
   const int T = w.tiles_i * w.tiles_r * w.tiles_c, n_ct = (g.Cout + 63) / 64;
-  int gx = ctx->num_cu / n_ct;
-  if (gx > T) gx = T;
-  if (gx < 1) gx = 1;
+  const int gx = persistent_grid_min1(ctx->num_cu / n_ct, T);
   if (!s3_opt_on(S3O_NO_WS_PP)) {
     // the ping-pong form: single-image tiles, two half-workgroups half a round apart
     const int T1 = g.N * w.tiles_r * w.tiles_c;
-    int gp = ctx->num_cu / n_ct;
-    if (gp > (T1 + 1) / 2) gp = (T1 + 1) / 2;
-    if (gp < 1) gp = 1;
+    const int gp = persistent_grid_min1(ctx->num_cu / n_ct, (T1 + 1) / 2);
     auto kern = res ? conv2d_ws_x3_pp_kernel<true> : conv2d_ws_x3_pp_kernel<false>;
     hipLaunchKernelGGL(kern, dim3(gp, n_ct), dim3(X_NT), X_LDS, ctx->stream, (const float*)x, (const char*)image,
                        bias, (const float*)res, (float*)y, w);

@@ -317,12 +317,7 @@ int launch_conv_dgrad_c2_x3_pack(s3_ctx* ctx, const ConvGeom& g, const float* w,
 }
 int launch_conv_dgrad_c2_x3(s3_ctx* ctx, const ConvGeom& g, const float* dy, const void* img, float* dx) {
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad_c2_x3_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 2 * DLDS1));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set, conv_dgrad_c2_x3_kernel, 2 * DLDS1)) return rc;
   const int tiles0 = (g.D[0] + DT0 - 1) / DT0, tiles1 = (g.D[1] + DT1 - 1) / DT1,
             tiles2 = (g.D[2] + DT2 - 1) / DT2;
   hipLaunchKernelGGL(conv_dgrad_c2_x3_kernel, dim3((unsigned)(g.N * tiles0 * tiles1 * tiles2)), dim3(DNT),
@@ -356,14 +351,9 @@ int launch_conv_dgrad_s2_x3_pack(s3_ctx* ctx, const ConvGeom& g, const float* w,
 int launch_conv_dgrad_s2_x3(s3_ctx* ctx, const ConvGeom& g, const float* dy, const void* img, float* dx,
                             const float* mask_y, float mask_slope) {
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad_s2_x3_kernel<2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 2 * SLDS1));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad_s2_x3_kernel<4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 2 * SLDS1));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            conv_dgrad_s2_x3_kernel<2>, 2 * SLDS1,
+                            conv_dgrad_s2_x3_kernel<4>, 2 * SLDS1)) return rc;
   const int U0 = (g.D[0] + 1) / 2, U1 = (g.D[1] + 1) / 2, U2 = (g.D[2] + 1) / 2;
   const int tiles0 = (U0 + ST0 - 1) / ST0, tiles1 = (U1 + ST1 - 1) / ST1, tiles2 = (U2 + ST2 - 1) / ST2;
   const int n_ct = (g.Cin + 63) / 64;

@@ -222,14 +222,9 @@ int launch_conv_halo32_fwd(s3_ctx* ctx, const ConvGeom& g, const void* xv, const
   const float* x = (const float*)xv;
   float* y = (float*)yv;
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo32_kernel<4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, HLDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo32_kernel<2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, HLDS));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            conv_halo32_kernel<4>, HLDS,
+                            conv_halo32_kernel<2>, HLDS)) return rc;
   const int tiles0 = (g.O[0] + HT0 - 1) / HT0, tiles1 = (g.O[1] + HT1 - 1) / HT1,
             tiles2 = (g.O[2] + HT2 - 1) / HT2;
   const int n_ct = (g.Cout + 63) / 64;

@@ -400,47 +400,32 @@ int launch_conv_halo_s2_fwd(s3_ctx* ctx, const ConvGeom& g, const void* x, const
   static S3DeviceOnce attr_set;
   if (halo_s2_k64_geom(g)) {
     static S3DeviceOnce k_attr;
-    if (!k_attr.done(ctx->device)) {
-      std::lock_guard<std::mutex> lk_k_attr(k_attr.m);
-      S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_s2_k64_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, K_LDS));
-      k_attr.mark(ctx->device);
-    }
-    const int t0 = (g.O[0] + KT0 - 1) / KT0, t1 = (g.O[1] + KT1 - 1) / KT1, t2 = (g.O[2] + KT2 - 1) / KT2;
-    const int n_tiles = g.N * t0 * t1 * t2;
-    int grid = ctx->num_cu;
-    if (grid > n_tiles) grid = n_tiles;
+    if (int rc = s3_lds_optin(ctx, k_attr, conv_halo_s2_k64_kernel, K_LDS)) return rc;
+    const TileCounts tc = tile_counts(g.N, g.O[0], KT0, g.O[1], KT1, g.O[2], KT2);
+    const int grid = persistent_grid(ctx->num_cu, tc.total);
     const size_t pbytes = (size_t)g.N * g.O[0] * g.O[1] * g.O[2] * 64 * sizeof(float);
     int rc = ensure_scratch(ctx, pbytes);
     if (rc) return rc;
     for (int ps = 0; ps < 2; ++ps)
       hipLaunchKernelGGL(conv_halo_s2_k64_kernel, dim3(grid), dim3(KNT), K_LDS, ctx->stream,
                          (const unsigned short*)x, (const unsigned short*)img, bias, (float*)ctx->scratch, y, g,
-                         t0, t1, t2, n_tiles, out_bf16, ps);
+                         tc.t0, tc.t1, tc.t2, tc.total, out_bf16, ps);
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_s2_kernel<2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_s2_kernel<1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS));
-    attr_set.mark(ctx->device);
-  }
-  const int tiles0 = (g.O[0] + ST0 - 1) / ST0, tiles1 = (g.O[1] + ST1 - 1) / ST1,
-            tiles2 = (g.O[2] + ST2 - 1) / ST2;
-  const int n_tiles = g.N * tiles0 * tiles1 * tiles2;
-  int grid = ctx->num_cu;
-  if (grid > n_tiles) grid = n_tiles;
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            conv_halo_s2_kernel<2>, S_LDS,
+                            conv_halo_s2_kernel<1>, S_LDS)) return rc;
+  const TileCounts tc = tile_counts(g.N, g.O[0], ST0, g.O[1], ST1, g.O[2], ST2);
+  const int grid = persistent_grid(ctx->num_cu, tc.total);
   if (g.Cout <= 16)
     hipLaunchKernelGGL(conv_halo_s2_kernel<1>, dim3(grid), dim3(SNT), S_LDS, ctx->stream,
-                       (const unsigned short*)x, (const unsigned short*)img, bias, y, g, tiles0, tiles1,
-                       tiles2, n_tiles, out_bf16);
+                       (const unsigned short*)x, (const unsigned short*)img, bias, y, g, tc.t0, tc.t1,
+                       tc.t2, tc.total, out_bf16);
   else
     hipLaunchKernelGGL(conv_halo_s2_kernel<2>, dim3(grid), dim3(SNT), S_LDS, ctx->stream,
-                       (const unsigned short*)x, (const unsigned short*)img, bias, y, g, tiles0, tiles1,
-                       tiles2, n_tiles, out_bf16);
+                       (const unsigned short*)x, (const unsigned short*)img, bias, y, g, tc.t0, tc.t1,
+                       tc.t2, tc.total, out_bf16);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }

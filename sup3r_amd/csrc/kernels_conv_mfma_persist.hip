@@ -744,16 +744,10 @@ bool conv_mfma_persist_dgrad_supported(const s3_ctx* ctx, const ConvGeom& g) {
 int launch_conv_mfma_persist_dgrad(s3_ctx* ctx, const ConvGeom& g, const void* dpre16, const void* image,
                                    float* dxp, int accumulate, int frame16) {
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_mfma_persist_kernel<4, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_mfma_persist_kernel<2, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_mfma_persist_kernel<4, true, 0, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            conv3_mfma_persist_kernel<4, true>, LDS_BYTES,
+                            conv3_mfma_persist_kernel<2, true>, LDS_BYTES,
+                            conv3_mfma_persist_kernel<4, true, 0, false, true>, LDS_BYTES)) return rc;
   if (frame16 && (accumulate || g.Cout != 64))
     S3_FAIL(ctx, S3_ESTATE, "persistent data gradient: a bf16 frame is written once, 64 channels wide");
   int gs0 = 1, gs1 = 1;
@@ -762,8 +756,7 @@ int launch_conv_mfma_persist_dgrad(s3_ctx* ctx, const ConvGeom& g, const void* d
   const int tiles0 = (gs0 * g.O[0] + 1) / 2, tiles1 = (gs1 * g.O[1] + TS1 - 1) / TS1,
             tiles2 = (g.O[2] + TS2 - 1) / TS2;
   const int n_tiles = tiles0 * tiles1 * tiles2;
-  int grid = ctx->num_cu;
-  if (grid > (n_tiles + 1) / 2) grid = (n_tiles + 1) / 2;
+  const int grid = persistent_grid(ctx->num_cu, (n_tiles + 1) / 2);
   auto kern = g.Cout <= 32 ? conv3_mfma_persist_kernel<2, true> : conv3_mfma_persist_kernel<4, true>;
   if (frame16) kern = conv3_mfma_persist_kernel<4, true, 0, false, true>;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), LDS_BYTES, ctx->stream,
@@ -817,39 +810,23 @@ int launch_conv_mfma_persist(s3_ctx* ctx, const ConvGeom& g, const void* x,
                              const void* image, const float* bias,
                              const void* res, void* y) {
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_mfma_persist_kernel<4, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_mfma_persist_kernel<2, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-#define S3_REP_ATTR(R)                                                                                          \
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_mfma_persist_kernel<4, false, R, true>),  \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));                     \
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_mfma_persist_kernel<4, false, R, false>), \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));                     \
-    S3_HIP(ctx, hipFuncSetAttribute(                                                                              \
-                    reinterpret_cast<const void*>(conv3_mfma_persist_kernel<4, false, R, true, false, 6>),        \
-                    hipFuncAttributeMaxDynamicSharedMemorySize, PGeo<6>::LDS_BYTES));                             \
-    S3_HIP(ctx, hipFuncSetAttribute(                                                                              \
-                    reinterpret_cast<const void*>(conv3_mfma_persist_kernel<4, false, R, false, false, 6>),       \
-                    hipFuncAttributeMaxDynamicSharedMemorySize, PGeo<6>::LDS_BYTES));
-    S3_REP_ATTR(2) S3_REP_ATTR(3) S3_REP_ATTR(4)
+#define S3_REP_ATTR(R)                                                                \
+  conv3_mfma_persist_kernel<4, false, R, true>, LDS_BYTES,                            \
+  conv3_mfma_persist_kernel<4, false, R, false>, LDS_BYTES,                           \
+  conv3_mfma_persist_kernel<4, false, R, true, false, 6>, PGeo<6>::LDS_BYTES,         \
+  conv3_mfma_persist_kernel<4, false, R, false, false, 6>, PGeo<6>::LDS_BYTES
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            conv3_mfma_persist_kernel<4, false>, LDS_BYTES,
+                            conv3_mfma_persist_kernel<2, false>, LDS_BYTES,
+                            S3_REP_ATTR(2), S3_REP_ATTR(3), S3_REP_ATTR(4),
+                            conv3_mfma_persist_kernel<4, false, 0, false, false, 6>, PGeo<6>::LDS_BYTES,
+                            conv3_mfma_persist_kernel<2, false, 0, false, false, 6>, PGeo<6>::LDS_BYTES)) return rc;
 #undef S3_REP_ATTR
-    S3_HIP(ctx, hipFuncSetAttribute(
-                    reinterpret_cast<const void*>(conv3_mfma_persist_kernel<4, false, 0, false, false, 6>),
-                    hipFuncAttributeMaxDynamicSharedMemorySize, PGeo<6>::LDS_BYTES));
-    S3_HIP(ctx, hipFuncSetAttribute(
-                    reinterpret_cast<const void*>(conv3_mfma_persist_kernel<2, false, 0, false, false, 6>),
-                    hipFuncAttributeMaxDynamicSharedMemorySize, PGeo<6>::LDS_BYTES));
-    attr_set.mark(ctx->device);
-  }
   // (tiles0 = half rows along s0, n_tiles = half-tiles: the kernel's work units)
   const int tiles0 = (g.O[0] + 1) / 2, tiles1 = (g.O[1] + TS1 - 1) / TS1,
             tiles2 = (g.O[2] + TS2 - 1) / TS2;
   const int n_tiles = g.N * tiles0 * tiles1 * tiles2;
-  int grid = ctx->num_cu;
-  if (grid > (n_tiles + 1) / 2) grid = (n_tiles + 1) / 2;
+  const int grid = persistent_grid(ctx->num_cu, (n_tiles + 1) / 2);
   const int n_ct = (g.Cout + 63) / 64;
   // (operands read through a fused temporal repeat: variants of their own with
   // the factor a compile-time constant — the index arithmetic with a run-time
@@ -877,9 +854,7 @@ int launch_conv_mfma_persist(s3_ctx* ctx, const ConvGeom& g, const void* x,
       (!rep || n_ct == 1) && !s3_opt_on(S3O_NO_PERSIST_STRIP)) {
     const int t1a = g.O[1] / TS1;
     const int na = g.N * tiles0 * t1a * tiles2, nb = (int)strip_halves;
-    int ga = ctx->num_cu, gb = ctx->num_cu;
-    if (ga > (na + 1) / 2) ga = (na + 1) / 2;
-    if (gb > (nb + 1) / 2) gb = (nb + 1) / 2;
+    const int ga = persistent_grid(ctx->num_cu, (na + 1) / 2), gb = persistent_grid(ctx->num_cu, (nb + 1) / 2);
     for (int ct = 0; ct < n_ct; ++ct) {          // (C_out > 64: one pair of launches per channel tile)
       const bool half = g.Cout - ct * 64 <= 32;
       const char* img = (const char*)image + (size_t)ct * 27 * 8192;

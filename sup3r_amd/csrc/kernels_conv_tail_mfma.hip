@@ -526,18 +526,11 @@ bool conv_tail_mfma_supported(const ConvGeom& g) {
 
 int launch_conv_tail_mfma(s3_ctx* ctx, const ConvGeom& g, const void* x,
                           const float* w, const float* bias, float* y, const float* aff) {
-  const int tiles0 = (g.O[0] + T0 - 1) / T0, tiles1 = (g.O[1] + T1 - 1) / T1,
-            tiles2 = (g.O[2] + T2 - 1) / T2;
-  const int n_tiles = g.N * tiles0 * tiles1 * tiles2;
+  const TileCounts tc = tile_counts(g.N, g.O[0], T0, g.O[1], T1, g.O[2], T2);
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tail_mfma_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BUF_BYTES));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tail_mfma_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BUF_BYTES));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            conv_tail_mfma_kernel<false>, 2 * BUF_BYTES,
+                            conv_tail_mfma_kernel<true>, 2 * BUF_BYTES)) return rc;
   const bool band = g.Cout == 2 && !s3_opt_has(S3O_NO_TAIL_BAND);
   // read per call: the parity tests flip it between two forwards
   const bool noslide = s3_opt_on(S3O_NO_TAIL_SLIDE);
@@ -546,12 +539,7 @@ int launch_conv_tail_mfma(s3_ctx* ctx, const ConvGeom& g, const void* x,
     return launch_conv_tail_sweep(ctx, g, x, w, bias, y, aff);
   if (band && g.O[0] >= 4 && !noslide) {
     static S3DeviceOnce slide_attr;
-    if (!slide_attr.done(ctx->device)) {
-      std::lock_guard<std::mutex> lk_slide_attr(slide_attr.m);
-      S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tail_slide_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, SLIDE_LDS));
-      slide_attr.mark(ctx->device);
-    }
+    if (int rc = s3_lds_optin(ctx, slide_attr, conv_tail_slide_kernel, SLIDE_LDS)) return rc;
     const int st1 = (g.O[1] + S1 - 1) / S1, st2 = (g.O[2] + S2 - 1) / S2;
     // rows per segment: a workgroup brings in seg + 2 planes per unit and the
     // launch lasts as long as its busiest workgroup — ceil(units / CUs) units.
@@ -573,18 +561,16 @@ int launch_conv_tail_mfma(s3_ctx* ctx, const ConvGeom& g, const void* x,
     }
     const int segs0 = (g.O[0] + seg - 1) / seg;
     const int n_units = g.N * segs0 * st1 * st2;
-    int sgrid = ctx->num_cu;
-    if (sgrid > n_units) sgrid = n_units;
+    const int sgrid = persistent_grid(ctx->num_cu, n_units);
     hipLaunchKernelGGL(conv_tail_slide_kernel, dim3(sgrid), dim3(NTH), SLIDE_LDS, ctx->stream,
                        (const unsigned short*)x, w, bias, y, g, segs0, st1, st2, n_units, seg, aff);
     S3_HIP(ctx, hipGetLastError());
     return S3_OK;
   }
-  int grid = ctx->num_cu;
-  if (grid > n_tiles) grid = n_tiles;
+  const int grid = persistent_grid(ctx->num_cu, tc.total);
   auto kern = band ? conv_tail_mfma_kernel<true> : conv_tail_mfma_kernel<false>;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NTH), 2 * BUF_BYTES, ctx->stream,
-                     (const unsigned short*)x, w, bias, y, g, tiles0, tiles1, tiles2, n_tiles, aff);
+                     (const unsigned short*)x, w, bias, y, g, tc.t0, tc.t1, tc.t2, tc.total, aff);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }

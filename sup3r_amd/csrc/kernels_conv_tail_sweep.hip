@@ -313,18 +313,11 @@ int launch_conv_tail_sweep(s3_ctx* ctx, const ConvGeom& g, const void* x, const 
   int nset = 1;
   if (!sweep_shape(ctx, g, sh, nset)) return S3_EINVAL;
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tail_sweep_kernel<1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tail_sweep_kernel<2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tail_sweep_kernel<3>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS));
-    attr_set.mark(ctx->device);
-  }
-  int grid = ctx->num_cu;
-  if (grid > sh.n_units) grid = sh.n_units;
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            conv_tail_sweep_kernel<1>, SW_LDS,
+                            conv_tail_sweep_kernel<2>, SW_LDS,
+                            conv_tail_sweep_kernel<3>, SW_LDS)) return rc;
+  const int grid = persistent_grid(ctx->num_cu, sh.n_units);
   auto kern = nset == 1 ? conv_tail_sweep_kernel<1>
                         : (nset == 2 ? conv_tail_sweep_kernel<2> : conv_tail_sweep_kernel<3>);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(SW_NTH), SW_NSLOT * sh.plane_bytes, ctx->stream,

@@ -581,17 +581,10 @@ static int launch_wgrad_bf16_reduce(s3_ctx* ctx, const float* partial, int n_par
   return S3_OK;
 }
 
-int bf_grid(const s3_ctx* ctx, const ConvGeom& g, int* n_tiles_out, int* t0,
-            int* t1, int* t2) {
-  const int tiles0 = (g.O[0] + BT0 - 1) / BT0, tiles1 = (g.O[1] + BT1 - 1) / BT1,
-            tiles2 = (g.O[2] + BT2 - 1) / BT2;
-  const int n_tiles = g.N * tiles0 * tiles1 * tiles2;
-  *n_tiles_out = n_tiles; *t0 = tiles0; *t1 = tiles1; *t2 = tiles2;
+int bf_grid(const s3_ctx* ctx, const ConvGeom& g, TileCounts& tc) {
+  tc = tile_counts(g.N, g.O[0], BT0, g.O[1], BT1, g.O[2], BT2);
   const int n_ct = (g.Cout + BCT - 1) / BCT;
-  int grid = ctx->num_cu / n_ct;
-  if (grid < 1) grid = 1;
-  if (grid > n_tiles) grid = n_tiles;
-  return grid;
+  return persistent_grid(ctx->num_cu / n_ct, tc.total);
 }
 
 // ===========================================================================
@@ -915,17 +908,12 @@ __global__ __launch_bounds__(BNT) void conv_wgrad_bf16_gen_kernel(
 }
 
 template <int CIB, int STR>
-int bf_gen_grid(const s3_ctx* ctx, const ConvGeom& g, int* n_tiles, int* t0, int* t1, int* t2) {
+int bf_gen_grid(const s3_ctx* ctx, const ConvGeom& g, TileCounts& tc) {
   using W = BfGen<CIB, STR>;
-  *t0 = (g.O[0] + W::T0 - 1) / W::T0; *t1 = (g.O[1] + W::T1 - 1) / W::T1;
-  *t2 = (g.O[2] + W::T2 - 1) / W::T2;
-  *n_tiles = g.N * *t0 * *t1 * *t2;
+  tc = tile_counts(g.N, g.O[0], W::T0, g.O[1], W::T1, g.O[2], W::T2);
   const int n_ct = (g.Cout + BCT - 1) / BCT;
   const int n_cit = (g.Cin + CIB * 16 - 1) / (CIB * 16);
-  int grid = ctx->num_cu / (n_ct * n_cit);
-  if (grid < 1) grid = 1;
-  if (grid > *n_tiles) grid = *n_tiles;
-  return grid;
+  return persistent_grid(ctx->num_cu / (n_ct * n_cit), tc.total);
 }
 
 // BF16X3 plans: 32-channel C_in tiles, hi + lo images (2 x the LDS of the bf16 form)
@@ -933,22 +921,17 @@ template <int STR>
 int bf_gen_launch_x3(s3_ctx* ctx, const ConvGeom& g, const float* x, const float* dy, float* dw,
                      float* partial, size_t partial_bytes, int accumulate) {
   using W = BfGen<2, STR>;
-  int n_tiles, t0, t1, t2;
-  const int grid = bf_gen_grid<2, STR>(ctx, g, &n_tiles, &t0, &t1, &t2);
+  TileCounts tc;
+  const int grid = bf_gen_grid<2, STR>(ctx, g, tc);
   const size_t need = (size_t)grid * 27 * g.Cin * g.Cout * sizeof(float);
   if (partial_bytes < need) S3_FAIL(ctx, S3_EINVAL, "wgrad_bf16_gen: partial buffer too small");
   auto kern = conv_wgrad_bf16_gen_kernel<2, STR, false, false, true>;
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * W::LDS)));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set, kern, 2 * W::LDS)) return rc;
   const int n_ct = (g.Cout + BCT - 1) / BCT;
   const int n_cit = (g.Cin + 31) / 32;
   hipLaunchKernelGGL(kern, dim3(grid, n_ct, n_cit), dim3(BNT), 2 * W::LDS, ctx->stream, x, dy, partial,
-                     g, t0, t1, t2, n_tiles);
+                     g, tc.t0, tc.t1, tc.t2, tc.total);
   S3_HIP(ctx, hipGetLastError());
   const int64_t wsize = (int64_t)27 * g.Cin * g.Cout;
   int rg = (int)((wsize + 255) / 256);
@@ -960,8 +943,8 @@ template <int CIB, int STR, bool IN16 = false>
 int bf_gen_launch(s3_ctx* ctx, const ConvGeom& g, const float* x, const float* dy, float* dw,
                   float* partial, size_t partial_bytes, int accumulate) {
   using W = BfGen<CIB, STR>;
-  int n_tiles, t0, t1, t2;
-  const int grid = bf_gen_grid<CIB, STR>(ctx, g, &n_tiles, &t0, &t1, &t2);
+  TileCounts tc;
+  const int grid = bf_gen_grid<CIB, STR>(ctx, g, tc);
   const size_t need = (size_t)grid * 27 * g.Cin * g.Cout * sizeof(float);
   if (partial_bytes < need) S3_FAIL(ctx, S3_EINVAL, "wgrad_bf16_gen: partial buffer too small");
   constexpr bool CAN_PF = CIB == 2 && IN16;
@@ -969,19 +952,17 @@ int bf_gen_launch(s3_ctx* ctx, const ConvGeom& g, const float* x, const float* d
   if constexpr (CAN_PF)
     if (!s3_opt_has(S3O_NO_WGRAD_GEN_PF)) kern = conv_wgrad_bf16_gen_kernel<CIB, STR, IN16, true>;
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_bf16_gen_kernel<CIB, STR, IN16>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)W::LDS));
-    if constexpr (CAN_PF)
-      S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_bf16_gen_kernel<CIB, STR, IN16, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)W::LDS));
-    attr_set.mark(ctx->device);
+  if constexpr (CAN_PF) {
+    if (int rc = s3_lds_optin(ctx, attr_set,
+                              conv_wgrad_bf16_gen_kernel<CIB, STR, IN16>, W::LDS,
+                              conv_wgrad_bf16_gen_kernel<CIB, STR, IN16, true>, W::LDS)) return rc;
+  } else {
+    if (int rc = s3_lds_optin(ctx, attr_set, conv_wgrad_bf16_gen_kernel<CIB, STR, IN16>, W::LDS)) return rc;
   }
   const int n_ct = (g.Cout + BCT - 1) / BCT;
   const int n_cit = (g.Cin + CIB * 16 - 1) / (CIB * 16);
   hipLaunchKernelGGL(kern, dim3(grid, n_ct, n_cit), dim3(BNT), W::LDS, ctx->stream, x, dy, partial,
-                     g, t0, t1, t2, n_tiles);
+                     g, tc.t0, tc.t1, tc.t2, tc.total);
   S3_HIP(ctx, hipGetLastError());
   const int64_t wsize = (int64_t)27 * g.Cin * g.Cout;
   int rg = (int)((wsize + 255) / 256);
@@ -1179,40 +1160,31 @@ __global__ __launch_bounds__(BNT) void conv2_wgrad_bf16_kernel(
 }
 
 template <int CIB, int STR>
-int bf_2d_grid(const s3_ctx* ctx, const ConvGeom& g, int* n_tiles, int* t1, int* t2) {
+int bf_2d_grid(const s3_ctx* ctx, const ConvGeom& g, TileCounts& tc) {
   using W = Bf2D<CIB, STR>;
-  *t1 = (g.O[0] + W::T1 - 1) / W::T1; *t2 = (g.O[1] + W::T2 - 1) / W::T2;
-  *n_tiles = g.N * *t1 * *t2;
+  tc = tile_counts(g.N, g.O[0], W::T1, g.O[1], W::T2);   // (t0, t1: the tiles along s1, s2)
   const int n_ct = (g.Cout + BCT - 1) / BCT;
   const int n_cit = (g.Cin + CIB * 16 - 1) / (CIB * 16);
   // one partial per workgroup: more workgroups than CUs would make the
   // fixed-order reduction (grid x 9 x C_in x C_out floats) the larger kernel
-  int grid = ctx->num_cu / (n_ct * n_cit);
-  if (grid < 1) grid = 1;
-  if (grid > *n_tiles) grid = *n_tiles;
-  return grid;
+  return persistent_grid(ctx->num_cu / (n_ct * n_cit), tc.total);
 }
 
 template <int CIB, int STR, bool IN16 = false, bool DY16 = false>
 int bf_2d_launch(s3_ctx* ctx, const ConvGeom& g, const float* x, const float* dy, float* dw,
                  float* partial, size_t partial_bytes, int accumulate) {
   using W = Bf2D<CIB, STR>;
-  int n_tiles, t1, t2;
-  const int grid = bf_2d_grid<CIB, STR>(ctx, g, &n_tiles, &t1, &t2);
+  TileCounts tc;
+  const int grid = bf_2d_grid<CIB, STR>(ctx, g, tc);
   const size_t need = (size_t)grid * 9 * g.Cin * g.Cout * sizeof(float);
   if (partial_bytes < need) S3_FAIL(ctx, S3_EINVAL, "wgrad_bf16_2d: partial buffer too small");
   auto kern = conv2_wgrad_bf16_kernel<CIB, STR, IN16, DY16>;
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)W::LDS));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set, kern, W::LDS)) return rc;
   const int n_ct = (g.Cout + BCT - 1) / BCT;
   const int n_cit = (g.Cin + CIB * 16 - 1) / (CIB * 16);
   hipLaunchKernelGGL(kern, dim3(grid, n_ct, n_cit), dim3(BNT), W::LDS, ctx->stream, x, dy, partial,
-                     g, t1, t2, n_tiles);
+                     g, tc.t0, tc.t1, tc.total);
   S3_HIP(ctx, hipGetLastError());
   const int64_t wsize = (int64_t)9 * g.Cin * g.Cout;
   int rg = (int)((wsize + 255) / 256);
@@ -1234,35 +1206,26 @@ bool conv_wgrad_bf16_supported(const ConvGeom& g, int precision) {
 }
 
 size_t conv_wgrad_bf16_partial_bytes(const s3_ctx* ctx, const ConvGeom& g) {
-  int nt, a, b, c;
-  const int grid = bf_grid(ctx, g, &nt, &a, &b, &c);
-  return (size_t)grid * 27 * 64 * g.Cout * sizeof(float);
+  TileCounts tc;
+  return (size_t)bf_grid(ctx, g, tc) * 27 * 64 * g.Cout * sizeof(float);
 }
 
 int launch_conv_wgrad_bf16(s3_ctx* ctx, const ConvGeom& g, const float* x,
                            const float* dy, float* dw, float* partial,
                            size_t partial_bytes, int accumulate, int x_bf16, int dy_bf16, int x3) {
-  int n_tiles, tiles0, tiles1, tiles2;
-  const int grid = bf_grid(ctx, g, &n_tiles, &tiles0, &tiles1, &tiles2);
+  TileCounts tc;
+  const int grid = bf_grid(ctx, g, tc);
   if (partial_bytes < conv_wgrad_bf16_partial_bytes(ctx, g))
     S3_FAIL(ctx, S3_EINVAL, "wgrad_bf16: partial buffer too small");
   if (x3 && (x_bf16 || dy_bf16)) S3_FAIL(ctx, S3_EINVAL, "wgrad_bf16: the split-bf16 kernel takes fp32 operands");
   if (dy_bf16 && (!x_bf16 || (g.Cout & 3))) S3_FAIL(ctx, S3_EINVAL, "wgrad_bf16: bf16 dPre needs bf16 x and C_out % 4 == 0");
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_bf16_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)BF_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_bf16_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)BF_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_bf16_kernel<true, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)BF_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_bf16_ws_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_x3_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            conv3_wgrad_bf16_kernel<false>, BF_LDS,
+                            conv3_wgrad_bf16_kernel<true>, BF_LDS,
+                            conv3_wgrad_bf16_kernel<true, true>, BF_LDS,
+                            conv3_wgrad_bf16_ws_kernel, WS_LDS,
+                            conv3_wgrad_x3_kernel, X3_LDS)) return rc;
   const int n_ct = (g.Cout + BCT - 1) / BCT;
   const int dbg = (int)s3_opt_int(S3O_WGRAD_DBG, 0);
   // wave-specialised variant: reflect padding, tiles that fit exactly, whole 16-B channel chunks
@@ -1272,20 +1235,20 @@ int launch_conv_wgrad_bf16(s3_ctx* ctx, const ConvGeom& g, const float* x,
                   (int64_t)g.O[0] * g.O[1] * g.O[2] * g.Cout < ((int64_t)1 << 31);
   if (x3)
     hipLaunchKernelGGL(conv3_wgrad_x3_kernel, dim3(grid, n_ct), dim3(BNT), X3_LDS, ctx->stream,
-                       x, dy, partial, g, tiles0, tiles1, tiles2, n_tiles);
+                       x, dy, partial, g, tc.t0, tc.t1, tc.t2, tc.total);
   else if (ws)
     hipLaunchKernelGGL(conv3_wgrad_bf16_ws_kernel, dim3(grid, n_ct), dim3(WS_NT), WS_LDS, ctx->stream,
-                       (const unsigned short*)x, (const unsigned short*)dy, partial, g, tiles0, tiles1, tiles2,
-                       n_tiles);
+                       (const unsigned short*)x, (const unsigned short*)dy, partial, g, tc.t0, tc.t1, tc.t2,
+                       tc.total);
   else if (dy_bf16)
     hipLaunchKernelGGL((conv3_wgrad_bf16_kernel<true, true>), dim3(grid, n_ct), dim3(BNT), BF_LDS,
-                       ctx->stream, x, dy, partial, g, tiles0, tiles1, tiles2, n_tiles, dbg);
+                       ctx->stream, x, dy, partial, g, tc.t0, tc.t1, tc.t2, tc.total, dbg);
   else if (x_bf16)
     hipLaunchKernelGGL(conv3_wgrad_bf16_kernel<true>, dim3(grid, n_ct), dim3(BNT), BF_LDS,
-                       ctx->stream, x, dy, partial, g, tiles0, tiles1, tiles2, n_tiles, dbg);
+                       ctx->stream, x, dy, partial, g, tc.t0, tc.t1, tc.t2, tc.total, dbg);
   else
     hipLaunchKernelGGL(conv3_wgrad_bf16_kernel<false>, dim3(grid, n_ct), dim3(BNT), BF_LDS,
-                       ctx->stream, x, dy, partial, g, tiles0, tiles1, tiles2, n_tiles, dbg);
+                       ctx->stream, x, dy, partial, g, tc.t0, tc.t1, tc.t2, tc.total, dbg);
   S3_HIP(ctx, hipGetLastError());
   const int64_t wsize = (int64_t)27 * 64 * g.Cout;
   return launch_wgrad_bf16_reduce(ctx, partial, grid, wsize, dw, accumulate, (int)((wsize + 255) / 256));

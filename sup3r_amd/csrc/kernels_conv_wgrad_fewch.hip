@@ -1073,40 +1073,31 @@ bool conv_wgrad_tail_supported(const ConvGeom& g, int precision) {
   return (int64_t)g.N * g.O[0] * g.O[1] * g.O[2] >= 65536;
 }
 
-static int tail_grid(const s3_ctx* ctx, const ConvGeom& g, int* t0, int* t1, int* t2, int* n_tiles) {
-  *t0 = (g.O[0] + TW0 - 1) / TW0; *t1 = (g.O[1] + TW1 - 1) / TW1; *t2 = (g.O[2] + TW2 - 1) / TW2;
-  *n_tiles = g.N * *t0 * *t1 * *t2;
+static int tail_grid(const s3_ctx* ctx, const ConvGeom& g, TileCounts& tc) {
+  tc = tile_counts(g.N, g.O[0], TW0, g.O[1], TW1, g.O[2], TW2);
   // (round 6: 3 or 4 workgroups per CU are no faster — 247 / 216 us against 211 —
   // the kernel is bound by its LDS fragment reads, not by occupancy)
-  int grid = 2 * ctx->num_cu;
-  if (grid > *n_tiles) grid = *n_tiles;
-  return grid;
+  return persistent_grid(2 * ctx->num_cu, tc.total);
 }
 
 size_t conv_wgrad_tail_partial_bytes(const s3_ctx* ctx, const ConvGeom& g) {
-  int a, b, c, nt;
-  return (size_t)tail_grid(ctx, g, &a, &b, &c, &nt) * 27 * 8 * g.Cout * sizeof(float);
+  TileCounts tc;
+  return (size_t)tail_grid(ctx, g, tc) * 27 * 8 * g.Cout * sizeof(float);
 }
 
 int launch_conv_wgrad_tail(s3_ctx* ctx, const ConvGeom& g, const float* x, const float* dy,
                            float* dw, float* partial, size_t partial_bytes, int accumulate,
                            int x_bf16) {
-  int t0, t1, t2, n_tiles;
-  const int grid = tail_grid(ctx, g, &t0, &t1, &t2, &n_tiles);
+  TileCounts tc;
+  const int grid = tail_grid(ctx, g, tc);
   if (partial_bytes < conv_wgrad_tail_partial_bytes(ctx, g))
     S3_FAIL(ctx, S3_EINVAL, "wgrad_tail: partial buffer too small");
   WSweepShape wsh;
   if (wgrad_tail_sweep_ok(g, x_bf16) && wsweep_shape(ctx, g, wsh)) {
     static S3DeviceOnce sweep_attr;
-    if (!sweep_attr.done(ctx->device)) {
-      std::lock_guard<std::mutex> lk(sweep_attr.m);
-      S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_tail_sweep_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS));
-      sweep_attr.mark(ctx->device);
-    }
+    if (int rc = s3_lds_optin(ctx, sweep_attr, conv_wgrad_tail_sweep_kernel, WS_LDS)) return rc;
     // (at most num_cu partials: the buffer is sized for 2 num_cu)
-    int sgrid = ctx->num_cu;
-    if (sgrid > wsh.n_units) sgrid = wsh.n_units;
+    int sgrid = persistent_grid(ctx->num_cu, wsh.n_units);
     if (sgrid > grid) sgrid = grid;
     int lds = WS_NSLOT * wsh.slot_bytes + WS_NDS * wsh.ds_bytes + 64;
     if (lds < WS_RED) lds = WS_RED;
@@ -1120,20 +1111,15 @@ int launch_conv_wgrad_tail(s3_ctx* ctx, const ConvGeom& g, const float* x, const
     return S3_OK;
   }
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_tail_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS));
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_tail_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set,
+                            conv_wgrad_tail_kernel<false>, TW_LDS,
+                            conv_wgrad_tail_kernel<true>, TW_LDS)) return rc;
   if (x_bf16)
     hipLaunchKernelGGL(conv_wgrad_tail_kernel<true>, dim3(grid), dim3(256), TW_LDS, ctx->stream, x, dy,
-                       partial, g, t0, t1, t2, n_tiles);
+                       partial, g, tc.t0, tc.t1, tc.t2, tc.total);
   else
     hipLaunchKernelGGL(conv_wgrad_tail_kernel<false>, dim3(grid), dim3(256), TW_LDS, ctx->stream, x, dy,
-                       partial, g, t0, t1, t2, n_tiles);
+                       partial, g, tc.t0, tc.t1, tc.t2, tc.total);
   S3_HIP(ctx, hipGetLastError());
   const int wsize = 27 * 8 * g.Cout;
   hipLaunchKernelGGL(wgrad_c2_partial_reduce, dim3((wsize + 15) / 16), dim3(256), 0, ctx->stream,

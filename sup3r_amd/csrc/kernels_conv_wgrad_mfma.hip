@@ -173,17 +173,10 @@ int launch_wgrad_partial_reduce(s3_ctx* ctx, const float* partial, int n_part, i
   return S3_OK;
 }
 
-int wgrad_grid(const s3_ctx* ctx, const ConvGeom& g, int* n_tiles_out, int* t0,
-               int* t1, int* t2) {
-  const int tiles0 = (g.O[0] + WT0 - 1) / WT0, tiles1 = (g.O[1] + WT1 - 1) / WT1,
-            tiles2 = (g.O[2] + WT2 - 1) / WT2;
-  const int n_tiles = g.N * tiles0 * tiles1 * tiles2;
-  *n_tiles_out = n_tiles; *t0 = tiles0; *t1 = tiles1; *t2 = tiles2;
+int wgrad_grid(const s3_ctx* ctx, const ConvGeom& g, TileCounts& tc) {
+  tc = tile_counts(g.N, g.O[0], WT0, g.O[1], WT1, g.O[2], WT2);
   const int n_ct = (g.Cout + WCT - 1) / WCT;
-  int grid = ctx->num_cu / n_ct;
-  if (grid < 1) grid = 1;
-  if (grid > n_tiles) grid = n_tiles;
-  return grid;
+  return persistent_grid(ctx->num_cu / n_ct, tc.total);
 }
 
 }  // namespace
@@ -196,28 +189,22 @@ bool conv_wgrad_mfma_supported(const ConvGeom& g) {
 }
 
 size_t conv_wgrad_mfma_partial_bytes(const s3_ctx* ctx, const ConvGeom& g) {
-  int nt, a, b, c;
-  const int grid = wgrad_grid(ctx, g, &nt, &a, &b, &c);
-  return (size_t)grid * 27 * 64 * g.Cout * sizeof(float);
+  TileCounts tc;
+  return (size_t)wgrad_grid(ctx, g, tc) * 27 * 64 * g.Cout * sizeof(float);
 }
 
 int launch_conv_wgrad_mfma(s3_ctx* ctx, const ConvGeom& g, const float* x,
                            const float* dy, float* dw, float* partial,
                            size_t partial_bytes, int accumulate) {
-  int n_tiles, tiles0, tiles1, tiles2;
-  const int grid = wgrad_grid(ctx, g, &n_tiles, &tiles0, &tiles1, &tiles2);
+  TileCounts tc;
+  const int grid = wgrad_grid(ctx, g, tc);
   if (partial_bytes < conv_wgrad_mfma_partial_bytes(ctx, g))
     S3_FAIL(ctx, S3_EINVAL, "wgrad_mfma: partial buffer too small");
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_mfma_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set, conv3_wgrad_mfma_kernel, WG_LDS)) return rc;
   const int n_ct = (g.Cout + WCT - 1) / WCT;
   hipLaunchKernelGGL(conv3_wgrad_mfma_kernel, dim3(grid, n_ct), dim3(WNT), WG_LDS,
-                     ctx->stream, x, dy, partial, g, tiles0, tiles1, tiles2, n_tiles);
+                     ctx->stream, x, dy, partial, g, tc.t0, tc.t1, tc.t2, tc.total);
   const int64_t wsize = (int64_t)27 * 64 * g.Cout;
   return launch_wgrad_partial_reduce(ctx, partial, grid, wsize, dw, accumulate);
 }
@@ -380,39 +367,29 @@ __global__ __launch_bounds__(512) void conv_wgrad_gen_kernel(
 }
 
 template <int CIB, int STR, int NB>
-int wgrad_gen_grid(const s3_ctx* ctx, const ConvGeom& g, int* n_tiles, int* t0, int* t1, int* t2) {
+int wgrad_gen_grid(const s3_ctx* ctx, const ConvGeom& g, TileCounts& tc) {
   using W = GenW<CIB, STR, NB>;
-  *t0 = (g.O[0] + W::T0 - 1) / W::T0; *t1 = (g.O[1] + W::T1 - 1) / W::T1;
-  *t2 = (g.O[2] + W::T2 - 1) / W::T2;
-  *n_tiles = g.N * *t0 * *t1 * *t2;
+  tc = tile_counts(g.N, g.O[0], W::T0, g.O[1], W::T1, g.O[2], W::T2);
   const int n_ct = (g.Cout + W::COT - 1) / W::COT;
   const int n_cit = (g.Cin + W::CIP - 1) / W::CIP;
-  int grid = ctx->num_cu / (n_ct * n_cit);
-  if (grid < 1) grid = 1;
-  if (grid > *n_tiles) grid = *n_tiles;
-  return grid;
+  return persistent_grid(ctx->num_cu / (n_ct * n_cit), tc.total);
 }
 
 template <int CIB, int STR, int NB>
 int wgrad_gen_launch(s3_ctx* ctx, const ConvGeom& g, const float* x, const float* dy,
                      float* dw, float* partial, size_t partial_bytes, int accumulate) {
   using W = GenW<CIB, STR, NB>;
-  int n_tiles, t0, t1, t2;
-  const int grid = wgrad_gen_grid<CIB, STR, NB>(ctx, g, &n_tiles, &t0, &t1, &t2);
+  TileCounts tc;
+  const int grid = wgrad_gen_grid<CIB, STR, NB>(ctx, g, tc);
   const size_t need = (size_t)grid * W::PS * 27 * g.Cin * g.Cout * sizeof(float);
   if (partial_bytes < need) S3_FAIL(ctx, S3_EINVAL, "wgrad_gen: partial buffer too small");
   auto kern = conv_wgrad_gen_kernel<CIB, STR, NB>;
   static S3DeviceOnce attr_set;
-  if (!attr_set.done(ctx->device)) {
-    std::lock_guard<std::mutex> lk_attr_set(attr_set.m);
-    S3_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)W::LDS));
-    attr_set.mark(ctx->device);
-  }
+  if (int rc = s3_lds_optin(ctx, attr_set, kern, W::LDS)) return rc;
   const int n_ct = (g.Cout + W::COT - 1) / W::COT;
   const int n_cit = (g.Cin + W::CIP - 1) / W::CIP;
   hipLaunchKernelGGL(kern, dim3(grid, n_ct, n_cit), dim3(512), W::LDS, ctx->stream, x, dy,
-                     partial, g, t0, t1, t2, n_tiles);
+                     partial, g, tc.t0, tc.t1, tc.t2, tc.total);
   const int64_t wsize = (int64_t)27 * g.Cin * g.Cout;
   return launch_wgrad_partial_reduce(ctx, partial, grid * W::PS, wsize, dw, accumulate);
 }

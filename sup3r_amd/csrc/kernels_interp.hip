@@ -32,17 +32,11 @@
 
 namespace {
 
-constexpr int kBlk = 256;
+constexpr int kBlk = kBlock;   // grid_for counts workgroups of this size
 constexpr int kMaxCh = 32;                  // channels of one surface call
 constexpr int kMaxFields = 3 * kMaxCh + 1;  // planes a tile may stage
 constexpr int kMaxTaps = 8;                 // upscaling: LANCZOS has 7
 constexpr size_t kMaxLds = 63 * 1024;       // dynamic LDS of a tile (+ 1 KB static)
-
-int grid_of(int64_t n, int num_cu) {
-  int64_t g = (n + kBlk - 1) / kBlk;
-  const int64_t cap = (int64_t)num_cu * 16;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
 
 // ---- st_interp --------------------------------------------------------------
 // axes: int32 i0 of the O1, O2, OT output indices, then their fp32 fractions
@@ -368,13 +362,13 @@ int surface_run(s3_ctx* ctx, const float* x, int n, int h, int w, int c, int s, 
   SurfKinds kk;
   for (int i = 0; i < kMaxCh; ++i) kk.k[i] = i < c ? kinds[i] : S3_SURF_OTHER;
   const int64_t lr_total = (int64_t)n * h * w * c;
-  hipLaunchKernelGGL(surface_prep_kernel, dim3(grid_of(lr_total, ctx->num_cu)), dim3(kBlk), 0, ctx->stream,
+  hipLaunchKernelGGL(surface_prep_kernel, dim3(grid_for(lr_total, ctx->num_cu, 16)), dim3(kBlk), 0, ctx->stream,
                      x, need_topo ? topo_lr : nullptr, planes, n, h, w, c, kk, (double)consts[0],
                      (double)consts[3], (double)consts[4]);
   S3_HIP(ctx, hipGetLastError());
   const int64_t hr_pix = (int64_t)h * s * w * s;
   if (any_pres) {
-    hipLaunchKernelGGL(pres_hr_kernel, dim3(grid_of(hr_pix, ctx->num_cu)), dim3(kBlk), 0, ctx->stream,
+    hipLaunchKernelGGL(pres_hr_kernel, dim3(grid_for(hr_pix, ctx->num_cu, 16)), dim3(kBlk), 0, ctx->stream,
                        topo_hr, g_hr, hr_pix, (double)consts[3], (double)consts[4]);
     S3_HIP(ctx, hipGetLastError());
   }
@@ -474,10 +468,10 @@ extern "C" int s3_st_interp(s3_ctx* ctx, const float* x, int n, int s1, int s2, 
   const bool vec = R % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
   const int64_t items = (int64_t)n * O1 * O2 * (vec ? R / 4 : R);
   if (vec)
-    hipLaunchKernelGGL(st_interp_kernel<4>, dim3(grid_of(items, ctx->num_cu)), dim3(kBlk), 0, ctx->stream, x, y,
+    hipLaunchKernelGGL(st_interp_kernel<4>, dim3(grid_for(items, ctx->num_cu, 16)), dim3(kBlk), 0, ctx->stream, x, y,
                        n, s1, s2, t, c, O1, O2, OT, ax);
   else
-    hipLaunchKernelGGL(st_interp_kernel<1>, dim3(grid_of(items, ctx->num_cu)), dim3(kBlk), 0, ctx->stream, x, y,
+    hipLaunchKernelGGL(st_interp_kernel<1>, dim3(grid_for(items, ctx->num_cu, 16)), dim3(kBlk), 0, ctx->stream, x, y,
                        n, s1, s2, t, c, O1, O2, OT, ax);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;

@@ -39,17 +39,10 @@
 
 namespace {
 
-constexpr int kBlk = 256;
+constexpr int kBlk = kBlock;   // grid_for counts workgroups of this size
 constexpr int kTileW = 32;     // columns of one image row per tile
 constexpr int kTileT = 16;     // time steps per tile
 constexpr int kMaxC = 16;
-
-inline int grid_for(int64_t n_threads, int num_cu) {
-  int64_t b = (n_threads + kBlk - 1) / kBlk;
-  const int64_t cap = (int64_t)num_cu * 8;
-  if (b > cap) b = cap;
-  return (int)(b < 1 ? 1 : b);
-}
 
 struct JoinGeom {
   int64_t t, h, w;
@@ -193,8 +186,7 @@ extern "C" int s3_branch_join(s3_ctx* ctx, const float* ya, int ca, const int* m
     }
     if (g.nrm) { g.mean[k] = mean_host[k]; g.sd[k] = std_host[k]; }
   }
-  const int64_t want = (int64_t)ctx->num_cu * 8;
-  const int grid = (int)(g.ntiles < want ? g.ntiles : want);
+  const int grid = grid_for(g.ntiles * kBlock, ctx->num_cu);   // a workgroup per tile, the rest by grid stride
   const size_t lds = (size_t)kTileT * (kTileW * g.nc + g.nc) * sizeof(float);   // <= 33 KiB
   hipLaunchKernelGGL(branch_join_kernel, dim3(grid), dim3(kBlk), lds, ctx->stream, g, ya, yb, x);
   S3_HIP(ctx, hipGetLastError());

@@ -23,14 +23,7 @@
 
 namespace {
 
-constexpr int kB = 256;
-
-inline int grid_of(int64_t n, int num_cu) {
-  int64_t b = (n + kB - 1) / kB;
-  const int64_t cap = (int64_t)num_cu * 8;
-  if (b > cap) b = cap;
-  return (int)(b < 1 ? 1 : b);
-}
+constexpr int kB = kBlock;   // grid_for counts workgroups of this size
 
 struct LGeom {
   int n, s1, s2, t, c, cu;   // cu = channels used
@@ -333,14 +326,14 @@ extern "C" int s3_lossmap_fwd(s3_ctx* ctx, int kind, const float* x, int n, int 
     case S3_LMAP_DERIV_T:
       if (kind == S3_LMAP_DERIV_S ? (s1 < 2 || s2 < 2) : t < 2)
         S3_FAIL(ctx, S3_EINVAL, "lossmap: derivative axis shorter than 2");
-      hipLaunchKernelGGL(deriv_fwd_kernel, dim3(grid_of(nel, ctx->num_cu)), dim3(kB), 0, ctx->stream,
+      hipLaunchKernelGGL(deriv_fwd_kernel, dim3(grid_for(nel, ctx->num_cu)), dim3(kB), 0, ctx->stream,
                          x, out, g, kind == S3_LMAP_DERIV_T);
       break;
     case S3_LMAP_MATERIAL: {
       const int hub = c_used / 2;
       if (hub < 1 || s1 < 2 || s2 < 2 || t < 2)
         S3_FAIL(ctx, S3_EINVAL, "lossmap: material derivative needs a (u, v) pair and axes >= 2");
-      hipLaunchKernelGGL(material_fwd_kernel, dim3(grid_of(nel / c_used * hub, ctx->num_cu)), dim3(kB),
+      hipLaunchKernelGGL(material_fwd_kernel, dim3(grid_for(nel / c_used * hub, ctx->num_cu)), dim3(kB),
                          0, ctx->stream, x, out, g, hub);
     } break;
     case S3_LMAP_MEAN_S:
@@ -353,7 +346,7 @@ extern "C" int s3_lossmap_fwd(s3_ctx* ctx, int kind, const float* x, int n, int 
         const int what = kind == S3_LMAP_MEAN_S ? 0 : 1 + q;
         hipLaunchKernelGGL(reduce_s_stage1, dim3(kSlabs, n), dim3(kB), 0, ctx->stream, x,
                            (const float*)nullptr, work, g, what);
-        hipLaunchKernelGGL(reduce_stage2, dim3(grid_of((int64_t)n * tc, ctx->num_cu)), dim3(kB), 0,
+        hipLaunchKernelGGL(reduce_stage2, dim3(grid_for((int64_t)n * tc, ctx->num_cu)), dim3(kB), 0,
                            ctx->stream, work, out + (int64_t)q * n * tc, n, kSlabs, tc, what,
                            what == 0 ? 1.f / (float)(s1 * s2) : 1.f);
       }
@@ -361,7 +354,7 @@ extern "C" int s3_lossmap_fwd(s3_ctx* ctx, int kind, const float* x, int n, int 
     case S3_LMAP_EXT_T: {
       const int64_t ne = (int64_t)n * s1 * s2 * c_used;
       for (int q = 0; q < 2; ++q)
-        hipLaunchKernelGGL(reduce_t_kernel, dim3(grid_of(ne, ctx->num_cu)), dim3(kB), 0, ctx->stream,
+        hipLaunchKernelGGL(reduce_t_kernel, dim3(grid_for(ne, ctx->num_cu)), dim3(kB), 0, ctx->stream,
                            x, (const float*)nullptr, out + q * ne, g, 1 + q);
     } break;
     default:
@@ -378,7 +371,7 @@ extern "C" int s3_lossmap_bwd(s3_ctx* ctx, int kind, const float* x, const float
   LGeom g{n, s1, s2, t, c, c_used};
   if (!geom_ok(ctx, g)) return S3_EINVAL;
   const int64_t nel = (int64_t)n * s1 * s2 * t * c_used;
-  const dim3 grid(grid_of(nel, ctx->num_cu));
+  const dim3 grid(grid_for(nel, ctx->num_cu));
   switch (kind) {
     case S3_LMAP_DERIV_S:
     case S3_LMAP_DERIV_T:
@@ -387,7 +380,7 @@ extern "C" int s3_lossmap_bwd(s3_ctx* ctx, int kind, const float* x, const float
       break;
     case S3_LMAP_MATERIAL: {
       const int hub = c_used / 2;
-      hipLaunchKernelGGL(material_bwd_kernel, dim3(grid_of(nel / c_used * hub, ctx->num_cu)), dim3(kB),
+      hipLaunchKernelGGL(material_bwd_kernel, dim3(grid_for(nel / c_used * hub, ctx->num_cu)), dim3(kB),
                          0, ctx->stream, x, g_out, d_x, g, hub);
     } break;
     case S3_LMAP_MEAN_S:
@@ -406,10 +399,10 @@ extern "C" int s3_lossmap_bwd(s3_ctx* ctx, int kind, const float* x, const float
           const int tc = t * c_used;
           hipLaunchKernelGGL(reduce_s_stage1, dim3(kSlabs, n), dim3(kB), 0, ctx->stream, x,
                              fx + q * ne, slab, g, 3);
-          hipLaunchKernelGGL(reduce_stage2, dim3(grid_of(ne, ctx->num_cu)), dim3(kB), 0, ctx->stream,
+          hipLaunchKernelGGL(reduce_stage2, dim3(grid_for(ne, ctx->num_cu)), dim3(kB), 0, ctx->stream,
                              slab, cnt + q * ne, n, kSlabs, tc, 0, 1.f);
         } else {
-          hipLaunchKernelGGL(reduce_t_kernel, dim3(grid_of(ne, ctx->num_cu)), dim3(kB), 0, ctx->stream,
+          hipLaunchKernelGGL(reduce_t_kernel, dim3(grid_for(ne, ctx->num_cu)), dim3(kB), 0, ctx->stream,
                              x, fx + q * ne, cnt + q * ne, g, 3);
         }
       }
@@ -433,7 +426,7 @@ extern "C" int s3_loss_mmd(s3_ctx* ctx, const float* a, int c_a, const float* b,
                            float* d_a) {
   if (!ctx || n < 1 || n_pos < 1 || c_used < 1 || c_used > 8 || c_used > c_a || c_used > c_b)
     return S3_EINVAL;
-  int nblk = grid_of(n_pos, ctx->num_cu);
+  int nblk = grid_for(n_pos, ctx->num_cu);
   if (nblk > 1024) nblk = 1024;
   int rc = ensure_scratch(ctx, (size_t)(nblk + 4) * sizeof(float));
   if (rc) return rc;
@@ -553,9 +546,9 @@ extern "C" int s3_dft_axis(s3_ctx* ctx, const float* in_re, const float* in_im, 
                                 " B of LDS per workgroup, the device has " + std::to_string(ctx->lds_max) +
                                 " (longest axis " + std::to_string(ctx->lds_max / (sizeof(float) * (2 * DFT_COLS + 2))) + ")");
   const int64_t ncol = outer * inner;
-  const void* kern = reinterpret_cast<const void*>(dft_axis_kernel);
+  // (the limit follows the axis: set per call, not once)
   if (lds > 64 * 1024)
-    S3_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = s3_lds_set(ctx, dft_axis_kernel, lds)) return rc;
   hipLaunchKernelGGL(dft_axis_kernel, dim3((unsigned)((ncol + DFT_COLS - 1) / DFT_COLS)), dim3(256),
                      lds, ctx->stream, in_re, in_im, out_re, out_im, outer, L, inner,
                      sign < 0 ? -1.f : 1.f);
@@ -570,10 +563,10 @@ extern "C" int s3_specmap(s3_ctx* ctx, int backward, const float* re, const floa
   if (!geom_ok(ctx, g)) return S3_EINVAL;
   const int64_t total = (int64_t)n * s1 * s2 * t * c;
   if (!backward)
-    hipLaunchKernelGGL(specmap_fwd_kernel, dim3(grid_of(total, ctx->num_cu)), dim3(kB), 0,
+    hipLaunchKernelGGL(specmap_fwd_kernel, dim3(grid_for(total, ctx->num_cu)), dim3(kB), 0,
                        ctx->stream, re, im, out0, g, mode3d);
   else
-    hipLaunchKernelGGL(specmap_bwd_kernel, dim3(grid_of(total, ctx->num_cu)), dim3(kB), 0,
+    hipLaunchKernelGGL(specmap_bwd_kernel, dim3(grid_for(total, ctx->num_cu)), dim3(kB), 0,
                        ctx->stream, re, im, g_y, out0, out1, g, mode3d);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;

@@ -30,7 +30,7 @@
 
 namespace {
 
-constexpr int kBlk = 256;
+constexpr int kBlk = kBlock;   // grid_for counts workgroups of this size
 constexpr int kWaves = kBlk / 64;
 constexpr int kMaxN = S3_SAMPLE_MAX_ORIGINS;
 constexpr int kMaxC = S3_SAMPLE_MAX_CHANNELS;
@@ -280,12 +280,10 @@ static int gather_impl(s3_ctx* ctx, const char* who, const float* data, int64_t 
       // memory bound: at most 8 workgroups per CU, the rest by grid stride
       const bool vec = aligned16(dst);
       const int64_t items = vec ? ((int64_t)g.total + 3) / 4 : (int64_t)g.total;
-      int64_t grid = (items + kBlk - 1) / kBlk;
-      const int64_t cap = (int64_t)ctx->num_cu * 8;
-      if (grid > cap) grid = cap;
+      const int grid = grid_for(items, ctx->num_cu);
       auto kernel = win ? (vec ? sample_gather_short_kernel<true, true> : sample_gather_short_kernel<false, true>)
                         : (vec ? sample_gather_short_kernel<true, false> : sample_gather_short_kernel<false, false>);
-      hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kBlk), 0, ctx->stream, g, data, dst, status);
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlk), 0, ctx->stream, g, data, dst, status);
     }
     S3_HIP(ctx, hipGetLastError());
   }

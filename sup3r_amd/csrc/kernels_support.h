@@ -1,21 +1,11 @@
 // What the streaming support kernels share (kernels_fold, kernels_pointwise,
 // kernels_reduce, kernels_optim, kernels_loss_content, kernels_chunk_io): the
-// launch shape of a grid-stride pass and the block sum.  For .hip files only.
+// block sum.  The launch shape of their grid-stride passes (kBlock, grid_for)
+// is launch_shape.h's, through common.h.  For .hip files only.
 #pragma once
 #include "common.h"
 
 namespace {
-
-// grid-stride loops, capped at ~8 blocks per CU
-constexpr int kBlock = 256;
-
-inline int grid_for(int64_t n_threads, int num_cu) {
-  int64_t b = (n_threads + kBlock - 1) / kBlock;
-  int64_t cap = (int64_t)num_cu * 8;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
 
 __device__ inline float wave_sum(float v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);

@@ -44,19 +44,13 @@ __global__ void time_mean_kernel(float* __restrict__ full, float* __restrict__ m
   }
 }
 
-int grid_tw(int64_t n, int num_cu) {
-  int64_t b = (n + 255) / 256;
-  const int64_t cap = (int64_t)num_cu * 16;
-  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace
 
 extern "C" int s3_time_window(s3_ctx* ctx, float* full, int64_t outer, int t, int c, int t0, int len,
                               float* window, int adjoint, float scale) {
   if (!ctx || !full || !window || outer < 1 || t < 1 || c < 1) return S3_EINVAL;
   if (t0 < 0 || len < 1 || t0 + len > t) S3_FAIL(ctx, S3_EINVAL, "time_window: slice outside the time axis");
-  hipLaunchKernelGGL(time_window_kernel, dim3(grid_tw(outer * len * c, ctx->num_cu)), dim3(256), 0, ctx->stream,
+  hipLaunchKernelGGL(time_window_kernel, dim3(grid_for(outer * len * c, ctx->num_cu, 16)), dim3(256), 0, ctx->stream,
                      full, window, outer, t, c, t0, len, adjoint, scale);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
@@ -66,7 +60,7 @@ extern "C" int s3_time_mean(s3_ctx* ctx, float* full, int64_t outer, int t, int 
                             float* mean, int adjoint, float scale) {
   if (!ctx || !full || !mean || outer < 1 || t < 1 || c < 1) return S3_EINVAL;
   if (t0 < 0 || len < 1 || t0 + len > t) S3_FAIL(ctx, S3_EINVAL, "time_mean: slice outside the time axis");
-  hipLaunchKernelGGL(time_mean_kernel, dim3(grid_tw(outer * c, ctx->num_cu)), dim3(256), 0, ctx->stream, full,
+  hipLaunchKernelGGL(time_mean_kernel, dim3(grid_for(outer * c, ctx->num_cu, 16)), dim3(256), 0, ctx->stream, full,
                      mean, outer, t, c, t0, len, adjoint, scale);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;

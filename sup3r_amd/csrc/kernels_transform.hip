@@ -14,7 +14,7 @@
 
 namespace {
 
-constexpr int kBlk = 256;
+constexpr int kBlk = kBlock;   // grid_for counts workgroups of this size
 constexpr int kMaxRadius = 32;
 
 struct GaussW {
@@ -115,12 +115,6 @@ __global__ void clip_channels_kernel(float* __restrict__ data, int c, int64_t n,
   }
 }
 
-int grid_of(int64_t n, int num_cu) {
-  int64_t g = (n + kBlk - 1) / kBlk;
-  const int64_t cap = (int64_t)num_cu * 16;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 }  // namespace
 
 extern "C" int s3_coarsen(s3_ctx* ctx, const float* hr, int n, int s1, int s2,
@@ -137,7 +131,7 @@ extern "C" int s3_coarsen(s3_ctx* ctx, const float* hr, int n, int s1, int s2,
     S3_FAIL(ctx, S3_EINVAL, "unknown temporal coarsening method");
   const int ot = method < 0 ? t : t / t_enhance;
   const int64_t total = (int64_t)n * (s1 / s_enhance) * (s2 / s_enhance) * ot * c;
-  hipLaunchKernelGGL(coarsen_kernel, dim3(grid_of(total, ctx->num_cu)), dim3(kBlk), 0,
+  hipLaunchKernelGGL(coarsen_kernel, dim3(grid_for(total, ctx->num_cu, 16)), dim3(kBlk), 0,
                      ctx->stream, hr, lr, n, s1, s2, t, c, s_enhance,
                      t_enhance < 1 ? 1 : t_enhance, method);
   S3_HIP(ctx, hipGetLastError());
@@ -155,7 +149,7 @@ extern "C" int s3_gaussian_smooth(s3_ctx* ctx, const float* x, int n, int s1,
   GaussW gw;
   for (int i = 0; i < 2 * radius + 1; ++i) gw.w[i] = weights_host[i];
   const int64_t total = (int64_t)n * s1 * s2 * t * c;
-  const int grid = grid_of(total, ctx->num_cu);
+  const int grid = grid_for(total, ctx->num_cu, 16);
   // scipy filters axis 0 first, then axis 1 (ndimage.gaussian_filter)
   hipLaunchKernelGGL(gauss_pass_kernel, dim3(grid), dim3(kBlk), 0, ctx->stream, x, tmp,
                      n, s1, s2, t, c, 0, radius, gw, channel_mask);
@@ -171,7 +165,7 @@ extern "C" int s3_invert_uv(s3_ctx* ctx, float* data, int64_t n_sp, int64_t t, i
   if (!ctx || !data || !cos_theta || !sin_theta) return S3_EINVAL;
   if (u_idx < 0 || v_idx < 0 || u_idx >= c || v_idx >= c || u_idx == v_idx)
     S3_FAIL(ctx, S3_EINVAL, "invert_uv: bad channel indices");
-  hipLaunchKernelGGL(invert_uv_kernel, dim3(grid_of(n_sp * t, ctx->num_cu)), dim3(kBlk), 0,
+  hipLaunchKernelGGL(invert_uv_kernel, dim3(grid_for(n_sp * t, ctx->num_cu, 16)), dim3(kBlk), 0,
                      ctx->stream, data, n_sp, t, c, u_idx, v_idx, cos_theta, sin_theta);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
@@ -200,7 +194,7 @@ extern "C" int s3_range_mask(s3_ctx* ctx, const float* data, int c, int ch, int6
                              float lo, float hi, unsigned char* mask) {
   if (!ctx || !data || !mask) return S3_EINVAL;
   if (ch < 0 || ch >= c) S3_FAIL(ctx, S3_EINVAL, "range_mask: bad channel index");
-  hipLaunchKernelGGL(range_mask_kernel, dim3(grid_of(n_pos, ctx->num_cu)), dim3(kBlk), 0, ctx->stream,
+  hipLaunchKernelGGL(range_mask_kernel, dim3(grid_for(n_pos, ctx->num_cu, 16)), dim3(kBlk), 0, ctx->stream,
                      data, c, ch, n_pos, lo, hi, mask);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
@@ -211,7 +205,7 @@ extern "C" int s3_fill_indexed(s3_ctx* ctx, float* data, int c, int ch, int64_t 
   if (!ctx || !data || !mask || !src) return S3_EINVAL;
   if (ch < 0 || ch >= c) S3_FAIL(ctx, S3_EINVAL, "fill_indexed: bad channel index");
   if (n_pos >= ((int64_t)1 << 31)) S3_FAIL(ctx, S3_EINVAL, "fill_indexed: 32-bit position indices");
-  hipLaunchKernelGGL(fill_indexed_kernel, dim3(grid_of(n_pos, ctx->num_cu)), dim3(kBlk), 0, ctx->stream,
+  hipLaunchKernelGGL(fill_indexed_kernel, dim3(grid_for(n_pos, ctx->num_cu, 16)), dim3(kBlk), 0, ctx->stream,
                      data, c, ch, n_pos, mask, src);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
@@ -223,7 +217,7 @@ extern "C" int s3_clip_channels(s3_ctx* ctx, float* data, int c, int64_t n_pos,
   if (c > 16) S3_FAIL(ctx, S3_EINVAL, "clip_channels supports at most 16 channels");
   Clip16 lim;
   for (int i = 0; i < c; ++i) { lim.lo[i] = min_host[i]; lim.hi[i] = max_host[i]; }
-  hipLaunchKernelGGL(clip_channels_kernel, dim3(grid_of(n_pos * c, ctx->num_cu)), dim3(kBlk), 0,
+  hipLaunchKernelGGL(clip_channels_kernel, dim3(grid_for(n_pos * c, ctx->num_cu, 16)), dim3(kBlk), 0,
                      ctx->stream, data, c, n_pos * c, lim);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
