@@ -936,6 +936,112 @@ int s3_bc_presrat(s3_ctx* ctx, const float* base, int64_t D, const float* bias, 
                   const int32_t* const* member, float* corrected, float* zero_rate, float* tau,
                   float* z_fg, float* tau_fut, float* k_factor, int32_t* status);
 
+/* ---- deriving input features on the device --------------------------------
+ * replaces the dask passes of sup3r/preprocessing/derivers (base.py,
+ * methods.py, utilities.py) and Interpolator.interp_to_level
+ * (sup3r/utilities/interpolation.py:13-173).  Features are PLANAR here: one
+ * fp32 tensor (s1 s2, t) per feature, a multi-level variable (s1 s2, t, L),
+ * levels innermost.  Element offsets are 64-bit.  Host tables (`_host`) are
+ * copied into the kernel arguments: no upload, no synchronisation in a call.
+ *
+ * s3_level_interp: a column is one (pixel, step), n_col = s1 s2 t of them.  Its
+ *   levels are the l_ml entries of the multi-level arrays followed by n_sl
+ *   single-level planes.  Level values of the first l_ml: S3_LI_LEV_COLUMN —
+ *   lev_ml (n_col, l_ml) minus, when topo is given, topo[column / t]
+ *   (topo_per_step = 0, topo (s1 s2)) or topo[column] (topo_per_step = 1), one
+ *   fp32 subtraction; S3_LI_LEV_VECTOR — lev_vec_host (l_ml) for every column.
+ *   Those of the planes: sl_level_host (n_sl).  var_ml_host: n_var device
+ *   pointers (n_col, l_ml); var_sl_host: n_var n_sl device pointers (n_col),
+ *   variable-major; out_host: n_var n_out device pointers (n_col),
+ *   variable-major.  Per (column, target) the two levels are chosen once, for
+ *   all variables, by the rule of get_level_masks (interpolation.py:17-70) on
+ *   d_i = |lev_i - target| over the levels that are not NaN, ties to the lowest
+ *   index: i1 = argmin d over lev < target, without one argmin d over all; i2 =
+ *   argmin d over lev >= target, without one argmin d over all but i1; an
+ *   empty set gives index 0.  S3_LI_LINEAR (_lin_interp :73-92): alpha = |lev2
+ *   - lev1| < 1e-3 ? 0 : (target - lev1) / (lev2 - lev1), out = var1 (1 - alpha)
+ *   + var2 alpha, every operation rounded to fp32 on its own (numpy's result,
+ *   bit for bit).  S3_LI_LOG: _log_interp (:95-112) in its order, fp32, logf.
+ *   One launch writes the n_var n_out planes; every input element is read once
+ *   (64 columns = one contiguous run, loaded 16 bytes per lane into LDS).
+ *   S3_EINVAL, before anything is launched: l_ml + n_sl outside 1 ..
+ *   S3_LI_MAX_LEVELS, n_sl > S3_LI_MAX_SINGLE, n_var outside 1 ..
+ *   S3_LI_MAX_VARS, n_out outside 1 .. S3_LI_MAX_TARGETS, a missing pointer.
+ * s3_derive_pointwise: out0 (, out1) (n_pix, t) from in0 (, in1), S3_DP_*:
+ *   UV_FROM_WSWD  transform_rotate_wind (derivers/utilities.py:146-201): in =
+ *                 windspeed, direction in degrees; out = u, v; cos_theta /
+ *                 sin_theta (n_pix) are the grid angle's tables
+ *   WSWD_FROM_UV  invert_uv (:204-258): in = u, v; out = speed, direction
+ *   SURFACE_RH    methods.py:63-72: in = d2m, temperature_2m
+ *   RATIO_MASKED  in0 / in1, NaN where step_flag[step] != 0 (methods.py:94-102)
+ *   CLOUD_MASK    in0 < in1 as 0 / 1, NaN where flagged (:152-160)
+ *   RATIO_CLIP01  max(min(in0 / in1, 1), 0), NaN kept (:128-130)
+ *   ADD           in0 + in1
+ *   SCALE         in0 p0
+ *   OFFSET        in0 + p0
+ *   BCAST_PIXEL   in0 (n_pix) along time
+ *   BCAST_TIME    in0 (t) along the pixels
+ *   All but the first three are single fp32 operations (numpy's bits).
+ * s3_time_flags: flags (t) int32, zeroed here, then OR-ed: S3_TF_LE — any x[p,
+ *   step, ch] <= threshold; S3_TF_NAN — any NaN; x is (n_pix, t, c).
+ * s3_stack_features: out (n_pix, t, c)[p, j, ch] = planes_host[ch][p, (j -
+ *   roll) mod t] (xr.Dataset.roll), c <= S3_STACK_MAX_PLANES.
+ * s3_level_stats: what Interpolator._check_lev_array (interpolation.py:
+ *   176-237) reports, of lev_ml (n_col, l_ml) minus topo as in
+ *   s3_level_interp: stats (S3_LS_WORDS uint64 on the device, zeroed here) =
+ *   the number of NaN levels, of columns without a NaN whose minimum is
+ *   above lo_target, of such columns whose maximum is below hi_target, of
+ *   all-NaN columns, and the extrema over the non-NaN values of the first
+ *   and of the last level as order keys: S3_LS_*_MAX holds key(max),
+ *   S3_LS_*_MIN holds 0xFFFFFFFF - key(min), key(v) = the float's bits with
+ *   the sign bit set for v >= 0 and all bits inverted for v < 0; a word left
+ *   at 0 means that every value of that level is NaN. */
+#define S3_LI_MAX_LEVELS 64
+#define S3_LI_MAX_SINGLE 8
+#define S3_LI_MAX_VARS 8
+#define S3_LI_MAX_TARGETS 16
+#define S3_LI_LINEAR 0
+#define S3_LI_LOG 1
+#define S3_LI_LEV_COLUMN 0
+#define S3_LI_LEV_VECTOR 1
+#define S3_DP_UV_FROM_WSWD 0
+#define S3_DP_WSWD_FROM_UV 1
+#define S3_DP_SURFACE_RH 2
+#define S3_DP_RATIO_MASKED 3
+#define S3_DP_CLOUD_MASK 4
+#define S3_DP_RATIO_CLIP01 5
+#define S3_DP_ADD 6
+#define S3_DP_SCALE 7
+#define S3_DP_OFFSET 8
+#define S3_DP_BCAST_PIXEL 9
+#define S3_DP_BCAST_TIME 10
+#define S3_TF_LE 0
+#define S3_TF_NAN 1
+#define S3_STACK_MAX_PLANES 32
+#define S3_LS_WORDS 8
+#define S3_LS_NAN 0
+#define S3_LS_BAD_MIN 1
+#define S3_LS_BAD_MAX 2
+#define S3_LS_ALL_NAN 3
+#define S3_LS_FIRST_MAX 4
+#define S3_LS_FIRST_MIN 5
+#define S3_LS_LAST_MAX 6
+#define S3_LS_LAST_MIN 7
+int s3_level_interp(s3_ctx* ctx, int64_t n_col, int64_t t, int l_ml, int n_sl, int lev_source,
+                    const float* lev_ml, const float* lev_vec_host, const float* topo, int topo_per_step,
+                    const float* sl_level_host, int n_var, const float* const* var_ml_host,
+                    const float* const* var_sl_host, int n_out, const float* target_host, int method,
+                    float* const* out_host);
+int s3_derive_pointwise(s3_ctx* ctx, int op, int64_t n_pix, int64_t t, const float* in0, const float* in1,
+                        const float* cos_theta, const float* sin_theta, const int32_t* step_flag, float p0,
+                        float* out0, float* out1);
+int s3_time_flags(s3_ctx* ctx, int mode, const float* x, int64_t n_pix, int64_t t, int c, float threshold,
+                  int32_t* flags);
+int s3_stack_features(s3_ctx* ctx, const float* const* planes_host, int c, int64_t n_pix, int64_t t,
+                      int64_t roll, float* out);
+int s3_level_stats(s3_ctx* ctx, const float* lev_ml, int64_t n_col, int64_t t, int l_ml, const float* topo,
+                   int topo_per_step, float lo_target, float hi_target, uint64_t* stats);
+
 /* ---- non-neural downscalers on the device ------------
  * replaces the host scipy / Pillow of the reference's LinearInterp and
  * SurfaceSpatialMetModel (sup3r/models/linear.py, sup3r/models/surface.py):

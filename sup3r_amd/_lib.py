@@ -55,6 +55,8 @@ EXPORTS = [
     's3_d2h_stream', 's3_host_alloc', 's3_host_free', 's3_d2h_async',
     's3_dma_d2h_begin', 's3_dma_wait',
     's3_invert_uv', 's3_clip_channels', 's3_range_mask', 's3_fill_indexed',
+    's3_level_interp', 's3_derive_pointwise', 's3_time_flags',
+    's3_stack_features', 's3_level_stats',
     's3_comm_unique_id', 's3_comm_init', 's3_params_allreduce_grads',
     's3_params_arm_allreduce',
     's3_allreduce_sum', 's3_params_broadcast', 's3_broadcast',
@@ -226,6 +228,15 @@ def lib():
         's3_clip_channels': (i32, [vp, vp, i32, i64, pf, pf]),
         's3_range_mask': (i32, [vp, vp, i32, i32, i64, f32, f32, vp]),
         's3_fill_indexed': (i32, [vp, vp, i32, i32, i64, vp, vp]),
+        's3_level_interp': (i32, [vp, i64, i64, i32, i32, i32, vp, pf, vp, i32,
+                                  pf, i32, C.POINTER(vp), C.POINTER(vp), i32,
+                                  pf, i32, C.POINTER(vp)]),
+        's3_derive_pointwise': (i32, [vp, i32, i64, i64, vp, vp, vp, vp, vp,
+                                      f32, vp, vp]),
+        's3_time_flags': (i32, [vp, i32, vp, i64, i64, i32, f32, vp]),
+        's3_stack_features': (i32, [vp, C.POINTER(vp), i32, i64, i64, i64,
+                                    vp]),
+        's3_level_stats': (i32, [vp, vp, i64, i64, i32, vp, i32, f32, f32, vp]),
         's3_host_register': (i32, [vp, vp, C.c_size_t]),
         's3_host_unregister': (i32, [vp, vp]),
         's3_d2h_window': (i32, [vp, vp, vp, i64, i64, i64, i64, i64, vp]),
@@ -358,6 +369,19 @@ BCC_MAX_SORT, BCC_MAX_GROUPS = 32768, 12
 BCC_AVG, BCC_MAX, BCC_MIN, BCC_SUM, BCC_NONE = range(5)
 BCC_NANSKIP, BCC_CS_RATIO, BCC_ROUND = 1, 2, 4
 BCC_PR_BIAS_NONFINITE, BCC_PR_FUT_NONFINITE, BCC_PR_INDEX = 0, 1, 2
+# s3_level_interp / s3_derive_pointwise / s3_time_flags / s3_stack_features:
+# limits, methods, level sources, ops, modes (include/sup3r_hip.h)
+LI_MAX_LEVELS, LI_MAX_SINGLE, LI_MAX_VARS, LI_MAX_TARGETS = 64, 8, 8, 16
+LI_LINEAR, LI_LOG = 0, 1
+LI_LEV_COLUMN, LI_LEV_VECTOR = 0, 1
+(DP_UV_FROM_WSWD, DP_WSWD_FROM_UV, DP_SURFACE_RH, DP_RATIO_MASKED,
+ DP_CLOUD_MASK, DP_RATIO_CLIP01, DP_ADD, DP_SCALE, DP_OFFSET, DP_BCAST_PIXEL,
+ DP_BCAST_TIME) = range(11)
+TF_LE, TF_NAN = 0, 1
+STACK_MAX_PLANES = 32
+LS_WORDS = 8
+(LS_NAN, LS_BAD_MIN, LS_BAD_MAX, LS_ALL_NAN, LS_FIRST_MAX, LS_FIRST_MIN,
+ LS_LAST_MAX, LS_LAST_MIN) = range(8)
 
 
 def last_error(ctx):
