@@ -1042,6 +1042,68 @@ int s3_stack_features(s3_ctx* ctx, const float* const* planes_host, int c, int64
 int s3_level_stats(s3_ctx* ctx, const float* lev_ml, int64_t n_col, int64_t t, int l_ml, const float* topo,
                    int topo_per_step, float lo_target, float hi_target, uint64_t* stats);
 
+/* ---- rasterising exogenous fields on the device ------------------------------
+ * replaces the host scipy / pandas of BaseExoRasterizer (sup3r/preprocessing/
+ * rasterizers/exo.py:294-458): KDTree(hr_lat_lon).query(source_lat_lon,
+ * distance_upper_bound=r) and the group mean per target of _get_data_2d /
+ * _get_data_3d.
+ *
+ * s3_exo_nearest: for each of n_src source points src (n_src, 2) fp32 (lat,
+ * lon) the nearest of the n_tgt target points tgt (n_tgt, 2) fp32 (any
+ * layout: the grid may be curvilinear) in the plain Euclidean distance of
+ * the two coordinates, in degrees, as the reference's tree measures it (no
+ * longitude wrap).  Arithmetic: the inputs widened to float64, d2 = dlat *
+ * dlat + dlon * dlon (two roundings of the products, one of the sum, nothing
+ * contracted); a target counts only if d2 < r * r, strictly; among equal d2
+ * the smallest target id wins (the tree's own choice on an exact tie follows
+ * its traversal: the one documented deviation).  nn[i] = the target id, n_tgt
+ * for a miss; dist (may be NULL) [i] = sqrt(d2) as float64, +inf for a miss.
+ * A NaN coordinate never matches: such a source is a miss, such a target is
+ * nobody's neighbour.
+ *   The search structure is built by the call, on the device, in work: the
+ * targets' bounding box (integer-atomic extrema of order keys), a uniform
+ * cell grid over it with cell side r (1 + 2^-16) — or larger: the side grows
+ * until there are at most min(2 n_tgt + 1024, 2^30) cells; the result does
+ * not depend on it —, an integer-atomic count per cell, a scan, a scatter of (lat, lon, id)
+ * into cell order.  A source examines the 3 x 3 cells around its own (a
+ * source outside the box: around the border cell it clamps to).
+ *
+ * s3_exo_group_mean: out[m, col_host[k]] = float32(float64(S) / n * scale)
+ * for every target m < n_tgt and k < t_used, where S is the sum and n the
+ * number of the values val[i, k] (val (n_src, t_used) fp32) that are no NaN
+ * and have nn[i] == m (an nn[i] outside [0, n_tgt) is a miss); NaN bits where
+ * n == 0.  out is (n_tgt, t_out) fp32; columns col_host does not name are not
+ * written.  nan_count: one 64-bit device word, zeroed here: the number of NaN
+ * cells written.
+ *   S is accumulated in fixed point with integer atomics only, so the bits do
+ * not depend on the order of arrival: a pre-pass takes E = floor(log2(max
+ * |val|)) over the finite values of the call; every value is rounded to a
+ * multiple of 2^(E - 61) (a 63-bit integer, exact for every value whose last
+ * mantissa bit is worth that or more: |val| >= 2^(E - 38)), its low 32 bits
+ * and the rest go to two 64-bit limbs per (target, column), which hold 2^31
+ * such terms without a carry between them; lanes of a wave that follow one
+ * another with the same target are summed before the atomic.  The sum of the
+ * limbs is rounded once to float64.  Error of the mean against the exact one,
+ * before the two roundings above: at most q = 2^(E - 62) <= 2^-62 max |val|.
+ * Infinite values are not supported (they saturate; nothing faults).
+ *   work holds S3_EXO_MAX_SLAB columns of limbs and counts at most; more
+ * columns are processed in slabs.
+ *
+ * Both are asynchronous on the context's stream and upload nothing.  work is
+ * at least what the *_work_bytes query returns, 8-byte aligned.  S3_EINVAL,
+ * before anything is launched: n_src or n_tgt below 1 or 2^31 and above, r
+ * that is not finite or not above 0, a missing pointer, work_bytes below the
+ * query's figure, t_used or t_out below 1, t_used above t_out, a col_host
+ * entry outside [0, t_out). */
+#define S3_EXO_MAX_SLAB 32
+int64_t s3_exo_nearest_work_bytes(int64_t n_tgt);
+int s3_exo_nearest(s3_ctx* ctx, const float* src, int64_t n_src, const float* tgt, int64_t n_tgt, double r,
+                   void* work, int64_t work_bytes, int32_t* nn, double* dist);
+int64_t s3_exo_group_mean_work_bytes(int64_t n_tgt, int64_t t_used);
+int s3_exo_group_mean(s3_ctx* ctx, const int32_t* nn, const float* val, int64_t n_src, int64_t n_tgt,
+                      int64_t t_used, int64_t t_out, const int32_t* col_host, double scale, void* work,
+                      int64_t work_bytes, float* out, uint64_t* nan_count);
+
 /* ---- non-neural downscalers on the device ------------
  * replaces the host scipy / Pillow of the reference's LinearInterp and
  * SurfaceSpatialMetModel (sup3r/models/linear.py, sup3r/models/surface.py):

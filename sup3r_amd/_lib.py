@@ -57,6 +57,8 @@ EXPORTS = [
     's3_invert_uv', 's3_clip_channels', 's3_range_mask', 's3_fill_indexed',
     's3_level_interp', 's3_derive_pointwise', 's3_time_flags',
     's3_stack_features', 's3_level_stats',
+    's3_exo_nearest_work_bytes', 's3_exo_nearest',
+    's3_exo_group_mean_work_bytes', 's3_exo_group_mean',
     's3_comm_unique_id', 's3_comm_init', 's3_params_allreduce_grads',
     's3_params_arm_allreduce',
     's3_allreduce_sum', 's3_params_broadcast', 's3_broadcast',
@@ -237,6 +239,13 @@ def lib():
         's3_stack_features': (i32, [vp, C.POINTER(vp), i32, i64, i64, i64,
                                     vp]),
         's3_level_stats': (i32, [vp, vp, i64, i64, i32, vp, i32, f32, f32, vp]),
+        's3_exo_nearest_work_bytes': (i64, [i64]),
+        's3_exo_nearest': (i32, [vp, vp, i64, vp, i64, C.c_double, vp, i64,
+                                 vp, vp]),
+        's3_exo_group_mean_work_bytes': (i64, [i64, i64]),
+        's3_exo_group_mean': (i32, [vp, vp, vp, i64, i64, i64, i64,
+                                    C.POINTER(i32), C.c_double, vp, i64, vp,
+                                    vp]),
         's3_host_register': (i32, [vp, vp, C.c_size_t]),
         's3_host_unregister': (i32, [vp, vp]),
         's3_d2h_window': (i32, [vp, vp, vp, i64, i64, i64, i64, i64, vp]),
@@ -382,6 +391,8 @@ STACK_MAX_PLANES = 32
 LS_WORDS = 8
 (LS_NAN, LS_BAD_MIN, LS_BAD_MAX, LS_ALL_NAN, LS_FIRST_MAX, LS_FIRST_MIN,
  LS_LAST_MAX, LS_LAST_MIN) = range(8)
+# s3_exo_group_mean: most columns of one slab (include/sup3r_hip.h)
+EXO_MAX_SLAB = 32
 
 
 def last_error(ctx):

@@ -11,8 +11,9 @@ is the in-memory counterpart of ``ForwardPassStrategy`` for the attributes
 the executor reads (``init_chunk`` strategy.py:520-581, ``node_chunks``
 :363-372, ``chunk_finished``, ``model_kwargs`` / ``model_class`` /
 ``allowed_const`` / ``invert_uv`` / ``nn_fill`` / ``output_workers``): file
-IO and exo rasterisation stay in sup3r (out of scope), here the
-lo-res domain and the exo fields are arrays.  Bias correction
+IO stays in sup3r (out of scope), here the lo-res domain and
+the exo fields are arrays; ``exo_handler_kwargs`` rasterises the fields from
+a source raster (``sup3r_amd.exo``).  Bias correction
 (``bias_correct_method`` / ``bias_correct_kwargs``, strategy.py:502-517) is
 not applied here: ``init_chunk`` attaches a ``bias_correct`` record to the raw
 chunk and the executor corrects the batch on the device (``sup3r_amd.bias``).
@@ -154,7 +155,13 @@ class ArrayStrategy:
     domain's time axis, which the monthly / QDM / PresRat methods need;
     ``input_lat_lon``: the low-res ``(s1, s2, 2)`` coordinates the factor
     tables are matched to when they carry ``latitude`` / ``longitude``.  The
-    chunks then carry a ``bias_correct`` record and raw ``input_data``."""
+    chunks then carry a ``bias_correct`` record and raw ``input_data``.
+
+    ``exo_handler_kwargs`` (strategy.py:583-628): feature -> keyword
+    arguments of ``sup3r_amd.exo.ExoDataHandler`` (``source_files``: an
+    ``ExoSource``, ...); ``exo_data`` is then rasterised from the source for
+    every model step, over ``input_lat_lon`` / ``input_time_index``.  Giving
+    both ``exo_data`` and ``exo_handler_kwargs`` is a ``ValueError``."""
 
     def __init__(self, domain, model_kwargs, fwp_chunk_shape, spatial_pad=1,
                  temporal_pad=1, model_class='Sup3rGan', exo_data=None,
@@ -163,8 +170,12 @@ class ArrayStrategy:
                  lat_lon=None, time_index=None, meta=None, s_enhance=None,
                  t_enhance=None, model=None, bias_correct_method=None,
                  bias_correct_kwargs=None, input_time_index=None,
-                 input_lat_lon=None):
+                 input_lat_lon=None, exo_handler_kwargs=None):
         from .forward_pass import get_model
+        if exo_handler_kwargs and exo_data is not None:
+            raise ValueError(
+                'give exo_data or exo_handler_kwargs, not both: the fields '
+                'are either passed or rasterised here')
         self.bias_correct_method = bias_correct_method
         self.bias_correct_kwargs = bias_correct_kwargs or {}
         self.input_time_index = input_time_index
@@ -190,6 +201,10 @@ class ArrayStrategy:
         self.model_kwargs = model_kwargs
         self.model_class = model_class
         self.spatial_pad, self.temporal_pad = spatial_pad, temporal_pad
+        self.exo_handler_kwargs = exo_handler_kwargs or {}
+        if self.exo_handler_kwargs:
+            model = model or get_model(model_class, model_kwargs)
+            exo_data = self.load_exo_data(model)
         self.exo_data = exo_data
         self.out_pattern = out_pattern
         self.allowed_const = allowed_const
@@ -252,6 +267,40 @@ class ArrayStrategy:
     def node_finished(self, node_index):
         return all(self.chunk_finished(i)
                    for i in self.node_chunks[node_index])
+
+    def get_exo_kwargs(self, model):
+        """strategy.py:583-603: one ``ExoDataHandler`` keyword set per exo
+        feature; the strategy's own ``input_lat_lon`` / ``input_time_index``
+        take the role of the input handler"""
+        from .exo import ExoInput
+        if self.input_lat_lon is None or self.input_time_index is None:
+            raise ValueError(
+                'exo_handler_kwargs needs input_lat_lon and input_time_index, '
+                'the low-res coordinates the fields are rasterised for')
+        exo_kwargs_list = []
+        for feature, kwargs in self.exo_handler_kwargs.items():
+            exo_kwargs = dict(kwargs)
+            exo_kwargs['feature'] = feature
+            exo_kwargs['model'] = model
+            exo_kwargs.setdefault('file_paths', ExoInput(
+                self.input_lat_lon, self.input_time_index))
+            exo_kwargs_list.append(exo_kwargs)
+        return exo_kwargs_list
+
+    def load_exo_data(self, model):
+        """strategy.py:612-628: every exo feature's steps over the whole
+        domain, rasterised by ``ExoDataHandler``; the fields are downloaded
+        here, once, for ``_exo_chunk`` to cut"""
+        from .exo import ExoDataHandler
+        from .utilities import ExoData
+        data = {}
+        for exo_kwargs in self.get_exo_kwargs(model):
+            data.update(ExoDataHandler(**exo_kwargs).data)
+        for entry in data.values():
+            for step in entry['steps']:
+                if hasattr(step['data'], 'detach'):
+                    step['data'] = step['data'].detach().cpu().numpy()
+        return ExoData(data)
 
     def _exo_chunk(self, lr_slices):
         """ExoData.get_chunk (exo.py:205-273): every step's field cut to the
