@@ -124,7 +124,8 @@ enum { S3_STAT_PERSIST_DGRAD = 0, /* trunk data gradients on the persistent kern
        S3_STAT_FOLD_ADD = 24,       /* ... added to an earlier gradient contribution            */
        S3_STAT_AXPY = 25,           /* skip accumulation, one element per lane                  */
        S3_STAT_AXPY4 = 26,          /* skip accumulation, four elements per lane                */
-       S3_STAT_COUNT = 27 };
+       S3_STAT_PERSIST_SKIPPRE = 27, /* trunk convs whose skip rows load under the last taps   */
+       S3_STAT_COUNT = 28 };
 int64_t s3_ctx_stat(const s3_ctx* ctx, int which);
 
 /* ---- parameter store ---------------------------------------------------

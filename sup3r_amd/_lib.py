@@ -323,7 +323,9 @@ STATS = {'persist_dgrad': 0, 'gconv_splitk': 1, 'bucket_elems': 2,
          'epi_d2s4': 15, 'epi_c4_bsum': 16, 'epi_d2s4_bsum': 17,
          'fold_gather': 18, 'fold_pad4': 19, 'fold_pad4_fr16': 20,
          'fold16x8': 21, 'fold_plain': 22, 'fold_masked': 23, 'fold_add': 24,
-         'axpy': 25, 'axpy4': 26}
+         'axpy': 25, 'axpy4': 26,
+         # persistent trunk convs launched on the skip-prefetch variant
+         'persist_skippre': 27}
 
 
 def option_names():

@@ -82,6 +82,7 @@
   X(NO_MFMA_BWD) \
   X(NO_PERSIST) \
   X(NO_PERSIST_DGRAD) \
+  X(NO_PERSIST_SKIPPRE) \
   X(NO_PERSIST_STRIP) \
   X(PERSIST2) \
   X(NO_REPEAT_FUSE) \

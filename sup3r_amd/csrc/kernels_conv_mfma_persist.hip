@@ -177,7 +177,20 @@ __global__ void pack_jobs_kernel(const S3PackJob* __restrict__ jobs) {
 // fold's sum of <= 8 frame cells is then the sum of bf16-rounded terms (the
 // rounding point tests/helpers.emulate_plan installs in the oracle's pad
 // adjoint).
-template <int NFV, bool DG, int REP = 0, bool RIN = false, bool F16 = false, int TW = 8>
+// SKP (plain 64 -> 64 trunk conv with a bf16 skip tensor, TW = 8): the eight
+// 16-B residual rows of a lane are requested behind the barrier of tap 25 and
+// waited for once behind tap 26, instead of requested and waited for in the
+// epilogue with all eight MFMA waves of the CU idle for one memory round trip
+// per tile.  The 32 registers they land in do not exist beside the tap loop
+// as it is (164 of 168), so tap 26 runs in a form that holds two filter
+// fragments and two position fragments at a time instead of four and five:
+// each k-step walks the N fragments in two halves and reads its A fragments
+// once per half.  Every accumulator still receives tap 0 .. 26 with k-step 0
+// before k-step 1: the sums are bit-identical to the other form's.
+// A tap takes ~ 3.3 us at the C2 shapes, longer than the round trip: ONE tap of
+// cover recovers the most (the low-register form is the slower one; 1 .. 6
+// taps measured in one run, profiles/skip_prefetch/NOTES.md).
+template <int NFV, bool DG, int REP = 0, bool RIN = false, bool F16 = false, int TW = 8, bool SKP = false>
 __global__ __launch_bounds__(NTHR) void conv3_mfma_persist_kernel(
     const unsigned short* __restrict__ x, const char* __restrict__ wimg,
     const float* __restrict__ bias, const unsigned short* __restrict__ res,
@@ -441,7 +454,8 @@ __global__ __launch_bounds__(NTHR) void conv3_mfma_persist_kernel(
   const int frow = lane & 15, kq = lane >> 4;
   const int mf0 = wave * MFW;
   const int row0 = (mf0 / TS1) * H1 + (mf0 % TS1);
-  unsigned a_addr[3][2], b_addr[4][2];
+  static_assert(!SKP || (NFV == 4 && !DG && REP == 0 && TW == 8), "skip prefetch: plain 64 -> 64 trunk conv");
+  unsigned a_addr[3][2], b_addr[2];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const int sw = (frow + c) & 7;
@@ -449,13 +463,13 @@ __global__ __launch_bounds__(NTHR) void conv3_mfma_persist_kernel(
     for (int ks = 0; ks < 2; ++ks)
       a_addr[c][ks] = (unsigned)((row0 * H2 + frow + c) * 128 + (((ks * 4 + kq) ^ sw) << 4));
   }
+  // filter fragment nf of a lane is slab row rho = nf*16 + frow; the swizzle
+  // term (rho >> 1) & 7 = (frow >> 1) & 7 does not depend on nf, so one
+  // address per k-step serves all four: nf*2048 (and the ring slot) go into
+  // the ds_read immediate
 #pragma unroll
-  for (int nf = 0; nf < 4; ++nf) {
-    const int rho = nf * 16 + frow;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-      b_addr[nf][ks] = (unsigned)(SLAB_OFF + rho * 128 + (((ks * 4 + kq) ^ ((rho >> 1) & 7)) << 4));
-  }
+  for (int ks = 0; ks < 2; ++ks)
+    b_addr[ks] = (unsigned)(SLAB_OFF + frow * 128 + (((ks * 4 + kq) ^ ((frow >> 1) & 7)) << 4));
   const float slope = g.act == S3_ACT_LEAKY ? g.alpha : (g.act == S3_ACT_RELU ? 0.f : 1.f);
   // this lane's two 8-channel chunks: block (bi, bj) and channel offset cc of
   // the depth-to-space store (b = 1: bi = bj = 0, cc = the channel itself)
@@ -507,52 +521,122 @@ __global__ __launch_bounds__(NTHR) void conv3_mfma_persist_kernel(
 #pragma unroll
     for (int m = 0; m < MFW; ++m)
       apre[m] = *reinterpret_cast<const bf16x8*>(smem + a_addr[0][0] + (m * H2) * 128);
+    // One tap (tb, tc) of halo row ta_off; ring slot of tap = (ta*9 + tb*3 +
+    // tc) % 3 = tc.  NEXT_A: whether the A fragments of the next tap are read.
+    // (a macro, not a lambda: see HALO_TABLE)
+#define TAP_FULL(ta_off, tb, tc, NEXT_A)                                                          \
+    {                                                                                              \
+      bf16x8 bfr[NFV];                                                                             \
+      /* ---- k-step 0: prefetched A, fresh B */                                                   \
+      _Pragma("unroll") for (int nf = 0; nf < NFV; ++nf)                                           \
+        bfr[nf] = *reinterpret_cast<const bf16x8*>(smem + b_addr[0] + nf * 2048 + (tc) * 8192);    \
+      _Pragma("unroll") for (int m = 0; m < MFW; ++m)                                              \
+        _Pragma("unroll") for (int nf = 0; nf < NFV; ++nf)                                         \
+          acc[m][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[nf], apre[m], acc[m][nf], 0, 0, 0); \
+      /* ---- k-step 1 */                                                                          \
+      _Pragma("unroll") for (int nf = 0; nf < NFV; ++nf)                                           \
+        bfr[nf] = *reinterpret_cast<const bf16x8*>(smem + b_addr[1] + nf * 2048 + (tc) * 8192);    \
+      _Pragma("unroll") for (int m = 0; m < MFW; ++m) {                                            \
+        const bf16x8 afr = *reinterpret_cast<const bf16x8*>(                                       \
+            smem + a_addr[tc][1] + (ta_off) + ((m + (tb)) * H2) * 128);                            \
+        _Pragma("unroll") for (int nf = 0; nf < NFV; ++nf)                                         \
+          acc[m][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[nf], afr, acc[m][nf], 0, 0, 0); \
+      }                                                                                            \
+      /* ---- A fragments of the next tap (k-step 0) */                                            \
+      {                                                                                            \
+        const int ntc = (tc) < 2 ? (tc) + 1 : 0;                                                   \
+        const int ntb = (tc) < 2 ? (tb) : ((tb) < 2 ? (tb) + 1 : 0);                               \
+        const unsigned nta_off = ((tc) == 2 && (tb) == 2) ? (ta_off) + H1 * H2 * 128 : (ta_off);   \
+        if (NEXT_A) {                                                                              \
+          _Pragma("unroll") for (int m = 0; m < MFW; ++m)                                          \
+            apre[m] = *reinterpret_cast<const bf16x8*>(                                            \
+                smem + a_addr[ntc][0] + nta_off + ((m + ntb) * H2) * 128);                         \
+        }                                                                                          \
+      }                                                                                            \
+      WG_BARRIER();                                                                                \
+    }
+    // The same tap with two filter fragments and two position fragments live
+    // instead of four and five (the skip variant's last tap): per k-step and
+    // half of the N fragments, the A fragment of position m + 1 is read
+    // before the two MFMAs of position m.  The scheduling barriers keep the
+    // order as written: left alone, the scheduler hoists every read to the
+    // top of the tap and the registers are needed all the same.
+#define TAP_LOW(ta_off, tb, tc)                                                                    \
+    {                                                                                              \
+      _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                           \
+        _Pragma("unroll") for (int nh = 0; nh < 2; ++nh) {                                         \
+          bf16x8 b2[2], a2[2];                                                                     \
+          _Pragma("unroll") for (int q = 0; q < 2; ++q)                                            \
+            b2[q] = *reinterpret_cast<const bf16x8*>(                                              \
+                smem + b_addr[ks] + (2 * nh + q) * 2048 + (tc) * 8192);                            \
+          a2[0] = *reinterpret_cast<const bf16x8*>(                                                \
+              smem + a_addr[tc][ks] + (ta_off) + ((tb) * H2) * 128);                               \
+          _Pragma("unroll") for (int m = 0; m < MFW; ++m) {                                        \
+            if (m + 1 < MFW)                                                                       \
+              a2[(m + 1) & 1] = *reinterpret_cast<const bf16x8*>(                                  \
+                  smem + a_addr[tc][ks] + (ta_off) + ((m + 1 + (tb)) * H2) * 128);                 \
+            _Pragma("unroll") for (int q = 0; q < 2; ++q)                                          \
+              acc[m][2 * nh + q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                        \
+                  b2[q], a2[m & 1], acc[m][2 * nh + q], 0, 0, 0);                                  \
+            __builtin_amdgcn_sched_barrier(0);                                                     \
+          }                                                                                        \
+        }                                                                                          \
+      }                                                                                            \
+      WG_BARRIER();                                                                                \
+    }
 #pragma unroll 1
-    for (int ta = 0; ta < 3; ++ta) {
+    for (int ta = 0; ta < (SKP ? 2 : 3); ++ta) {
       const unsigned ta_off = (unsigned)(ta * H1 * H2 * 128);
 #pragma unroll
       for (int tb = 0; tb < 3; ++tb) {
 #pragma unroll
-        for (int tc = 0; tc < 3; ++tc) {
-          // ring slot of tap = (ta*9 + tb*3 + tc) % 3 = tc
-          bf16x8 bfr[NFV];
-          // ---- k-step 0: prefetched A, fresh B
-#pragma unroll
-          for (int nf = 0; nf < NFV; ++nf)
-            bfr[nf] = *reinterpret_cast<const bf16x8*>(smem + b_addr[nf][0] + tc * 8192);
-#pragma unroll
-          for (int m = 0; m < MFW; ++m)
-#pragma unroll
-            for (int nf = 0; nf < NFV; ++nf)
-              acc[m][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[nf], apre[m], acc[m][nf], 0, 0, 0);
-          // ---- k-step 1
-#pragma unroll
-          for (int nf = 0; nf < NFV; ++nf)
-            bfr[nf] = *reinterpret_cast<const bf16x8*>(smem + b_addr[nf][1] + tc * 8192);
-#pragma unroll
-          for (int m = 0; m < MFW; ++m) {
-            const bf16x8 afr = *reinterpret_cast<const bf16x8*>(
-                smem + a_addr[tc][1] + ta_off + ((m + tb) * H2) * 128);
-#pragma unroll
-            for (int nf = 0; nf < NFV; ++nf)
-              acc[m][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[nf], afr, acc[m][nf], 0, 0, 0);
-          }
-          // ---- A fragments of the next tap (k-step 0)
-          {
-            const int ntc = tc < 2 ? tc + 1 : 0;
-            const int ntb = tc < 2 ? tb : (tb < 2 ? tb + 1 : 0);
-            const unsigned nta_off = (tc == 2 && tb == 2) ? ta_off + H1 * H2 * 128 : ta_off;
-            if (!(tc == 2 && tb == 2) || ta < 2) {
-#pragma unroll
-              for (int m = 0; m < MFW; ++m)
-                apre[m] = *reinterpret_cast<const bf16x8*>(
-                    smem + a_addr[ntc][0] + nta_off + ((m + ntb) * H2) * 128);
-            }
-          }
-          WG_BARRIER();
-        }
+        for (int tc = 0; tc < 3; ++tc) TAP_FULL(ta_off, tb, tc, (!(tc == 2 && tb == 2) || ta < 2))
       }
     }
+    // offset(m, h) of the epilogue = position part (m) + chunk part (h), element
+    // offsets within sample n: both per-lane scalars
+    unsigned e_pos[MFW];
+    bool e_ok[MFW];
+#define EPI_POS()                                                                                  \
+    _Pragma("unroll") for (int m = 0; m < MFW; ++m) {                                              \
+      const int mf = mf0 + m;                                                                      \
+      const int o0 = org0 + mf / TS1, o1 = org1 + mf % TS1, o2 = org2 + frow;                      \
+      e_ok[m] = o0 < g.O[0] && o1 < g.O[1] && o2 < g.O[2];                                         \
+      e_pos[m] = (unsigned)(((o0 * db * (g.O[1] * db) + o1 * db) * g.O[2] + o2) * cpo);            \
+    }
+    uint4 rres[MFW][2];   // the residual rows of this lane's chunks
+    if constexpr (SKP) {
+      // ---- halo row 2 in straight-line code (the rolled loop above ends with
+      // the A fragments of tap 18 read): taps 18 .. 25 as above — tap 25 reads
+      // no A ahead, the low form reads its own
+      constexpr unsigned ta_off = (unsigned)(2 * H1 * H2 * 128);
+#pragma unroll
+      for (int t8 = 0; t8 < 8; ++t8) TAP_FULL(ta_off, t8 / 3, t8 % 3, (t8 < 7))
+      // residual rows of this lane: rows outside the tensor (ragged tiles)
+      // read offset 0 of the sample, a legal address, and are masked at the
+      // store.  Nothing may touch rpre before the wait behind tap 26.
+      EPI_POS()
+      const unsigned short* rb = res + (size_t)n * g.O[0] * g.O[1] * g.O[2] * 64;
+      u32x4 rpre[MFW][2];
+#pragma unroll
+      for (int m = 0; m < MFW; ++m)
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh)
+          rpre[m][hh] = ld16_async(rb, e_ok[m] ? (e_pos[m] + c_off[hh]) * 2u : 0u);
+      TAP_LOW(ta_off, 2, 2)   // tap 26
+      WAIT_VM(0);
+      // (ordered behind the wait, like every volatile asm: the plain C that
+      // follows cannot be scheduled above it)
+#pragma unroll
+      for (int m = 0; m < MFW; ++m)
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          asm volatile("" : "+v"(rpre[m][hh]));
+          rres[m][hh] = make_uint4(rpre[m][hh][0], rpre[m][hh][1], rpre[m][hh][2], rpre[m][hh][3]);
+        }
+    }
+#undef TAP_FULL
+#undef TAP_LOW
 
     if constexpr (DG) {
       // ---- fp32 store over the stacked frames: S = q E + u per axis
@@ -596,24 +680,17 @@ __global__ __launch_bounds__(NTHR) void conv3_mfma_persist_kernel(
     // hi-res cell's channels: block (i, j) = chunk / (C_out / b^2) lands at
     // (o0 b + i, o1 b + j, o2).  Addresses are element offsets within sample n.
     const size_t e_base = (size_t)n * g.O[0] * g.O[1] * g.O[2] * g.Cout;
-    // offset(m, h) = position part (m) + chunk part (h): both per-lane scalars
-    unsigned e_pos[MFW];
-    bool e_ok[MFW];
-#pragma unroll
-    for (int m = 0; m < MFW; ++m) {
-      const int mf = mf0 + m;
-      const int o0 = org0 + mf / TS1, o1 = org1 + mf % TS1, o2 = org2 + frow;
-      e_ok[m] = o0 < g.O[0] && o1 < g.O[1] && o2 < g.O[2];
-      e_pos[m] = (unsigned)(((o0 * db * (g.O[1] * db) + o1 * db) * g.O[2] + o2) * cpo);
+    if constexpr (!SKP) {
+      EPI_POS()
     }
+#undef EPI_POS
     auto chunk_off = [&](int m, int h, bool& ok) __attribute__((always_inline)) {
       ok = c_ok[h] && e_ok[m] && 2 * h < NFV;
       return e_pos[m] + c_off[h];
     };
-    // residual rows first (all loads in flight together), then activation +
-    // add + 16-B stores
-    uint4 rres[MFW][2];
-    if (res) {
+    // residual rows first (all loads in flight together; SKP: they arrived
+    // under tap 26), then activation + add + 16-B stores
+    if (!SKP && res) {
       // a residual read through a fused temporal repeat (d2s == 1, cpo = 64):
       // cell o2 of the skip tensor is cell o2 / res_rep of what is stored
       const bool rr = REP > 1 && !DG && g.res_rep > 1;       // (then res_rep == REP)
@@ -655,7 +732,7 @@ __global__ __launch_bounds__(NTHR) void conv3_mfma_persist_kernel(
           const float sa = slope * a;
           asm("v_max_f32 %0, %1, %2" : "=v"(v[q]) : "v"(a), "v"(sa));
         }
-        if (res) {
+        if (SKP || res) {
           const uint4 r = rres[m][h];
           v[0] += bf_lo(r.x); v[1] += bf_hi(r.x); v[2] += bf_lo(r.y); v[3] += bf_hi(r.y);
           v[4] += bf_lo(r.z); v[5] += bf_hi(r.z); v[6] += bf_lo(r.w); v[7] += bf_hi(r.w);
@@ -818,6 +895,7 @@ int launch_conv_mfma_persist(s3_ctx* ctx, const ConvGeom& g, const void* x,
   if (int rc = s3_lds_optin(ctx, attr_set,
                             conv3_mfma_persist_kernel<4, false>, LDS_BYTES,
                             conv3_mfma_persist_kernel<2, false>, LDS_BYTES,
+                            conv3_mfma_persist_kernel<4, false, 0, false, false, 8, true>, LDS_BYTES,
                             S3_REP_ATTR(2), S3_REP_ATTR(3), S3_REP_ATTR(4),
                             conv3_mfma_persist_kernel<4, false, 0, false, false, 6>, PGeo<6>::LDS_BYTES,
                             conv3_mfma_persist_kernel<2, false, 0, false, false, 6>, PGeo<6>::LDS_BYTES)) return rc;
@@ -834,6 +912,10 @@ int launch_conv_mfma_persist(s3_ctx* ctx, const ConvGeom& g, const void* x,
   // next to the hand-ordered in-flight loads is not safe)
   const int rep = g.in_rep > 1 ? g.in_rep : (g.res_rep > 1 ? g.res_rep : 0);
   const bool rin = g.in_rep > 1;
+  // a plain trunk conv with a skip tensor: the variant that loads the skip rows
+  // under its last taps (read per launch, as NO_PERSIST is)
+  const bool skp = res && !rep && g.d2s == 1 && g.Cout == 64 && !s3_opt_on(S3O_NO_PERSIST_SKIPPRE);
+  if (skp) ++ctx->stat[S3_STAT_PERSIST_SKIPPRE];
   ConvGeom gk = g;                 // what the kernel sees
   if (rep) {
     bool ok = conv_mfma_persist_rep_ok(rep) && g.Cout == 64 && g.d2s == 1 &&
@@ -861,6 +943,7 @@ int launch_conv_mfma_persist(s3_ctx* ctx, const ConvGeom& g, const void* x,
       auto k8 = half ? conv3_mfma_persist_kernel<2, false> : conv3_mfma_persist_kernel<4, false>;
       auto k6 = half ? conv3_mfma_persist_kernel<2, false, 0, false, false, 6>
                      : conv3_mfma_persist_kernel<4, false, 0, false, false, 6>;
+      if (skp) k8 = conv3_mfma_persist_kernel<4, false, 0, false, false, 8, true>;   // (the 8-column launch only)
       if (rep == 2) {
         k8 = rin ? conv3_mfma_persist_kernel<4, false, 2, true> : conv3_mfma_persist_kernel<4, false, 2, false>;
         k6 = rin ? conv3_mfma_persist_kernel<4, false, 2, true, false, 6>
@@ -887,6 +970,7 @@ int launch_conv_mfma_persist(s3_ctx* ctx, const ConvGeom& g, const void* x,
     // a last tile with <= 32 valid channels computes two N fragments only
     const bool half = g.Cout - ct * 64 <= 32;
     auto kern = half ? conv3_mfma_persist_kernel<2, false> : conv3_mfma_persist_kernel<4, false>;
+    if (skp) kern = conv3_mfma_persist_kernel<4, false, 0, false, false, 8, true>;
     if (rep == 2) kern = rin ? conv3_mfma_persist_kernel<4, false, 2, true> : conv3_mfma_persist_kernel<4, false, 2, false>;
     else if (rep == 3) kern = rin ? conv3_mfma_persist_kernel<4, false, 3, true> : conv3_mfma_persist_kernel<4, false, 3, false>;
     else if (rep == 4) kern = rin ? conv3_mfma_persist_kernel<4, false, 4, true> : conv3_mfma_persist_kernel<4, false, 4, false>;
