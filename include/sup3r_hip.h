@@ -747,6 +747,36 @@ int s3_cc_window_gather(s3_ctx* ctx, const float* data, int64_t S1, int64_t S2, 
 int s3_nn_fill(s3_ctx* ctx, float* x, int n, int s1, int s2, int t, int C, int channel,
                void* work, int* count);
 
+/* ---- per-feature statistics and normalisation of a resident cube -----------
+ * replaces the host pass of StatsCollection (sup3r/preprocessing/collections/
+ * stats.py:51-74: .mean(skipna=True) / .std(skipna=True) of every feature over
+ * all of space and time) and of Sup3rX.normalize (accessor.py:356-361) over a
+ * channels-last fp32 cube x (n_pos, c), c <= S3_STATS_MAX_CHANNELS, any c in
+ * that range, 4-byte aligned (16-byte loads run between a head and a tail of up
+ * to 3 floats); element offsets are 64-bit.
+ *
+ * s3_channel_moments: out[c][3] (DEVICE, fp64) = the number of non-NaN values
+ * of the channel, their mean, and the sum of their squared deviations from it
+ * (std = sqrt(out[2] / out[0]), ddof 0), from ONE read of the cube: shifted
+ * sums in fp64, folded in a fixed order without atomics — two calls on the same
+ * cube give the same bits.  +-inf counts as a value: the mean is +-inf (NaN for
+ * both signs) and the third word NaN, as numpy's.  A channel without a value:
+ * (0, 0, 0).  Uses the context's scratch block for the workgroups' partials.
+ *
+ * s3_normalize_channels: x[p][q] = (x[p][q] - mean_host[q]) / std_host[q] in
+ * place for every q with flag_host[q] != 0, as a correctly rounded fp32
+ * subtraction followed by a correctly rounded fp32 division — bit for bit
+ * numpy's float32 (x - m) / s, which neither a multiply by a reciprocal nor
+ * s3_affine_channels gives.  Unflagged channels keep every bit; NaN stays NaN.
+ * The three host arrays (c entries each) travel in the kernel arguments.
+ *
+ * Both are asynchronous on the context's stream.  S3_EINVAL: c outside 1 ..
+ * S3_STATS_MAX_CHANNELS, n_pos < 1, a misaligned pointer. */
+#define S3_STATS_MAX_CHANNELS 64
+int s3_channel_moments(s3_ctx* ctx, const float* x, int64_t n_pos, int c, double* out);
+int s3_normalize_channels(s3_ctx* ctx, float* x, int64_t n_pos, int c, const float* mean_host,
+                          const float* std_host, const unsigned char* flag_host);
+
 /* ---- bias correction of forward-pass chunks on the device ------------------
  * replaces the host numpy / rex of ForwardPassStrategy.prep_chunk_data
  * (sup3r/pipeline/strategy.py:502-517 -> bias_correct_features ->

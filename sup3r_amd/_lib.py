@@ -46,7 +46,7 @@ EXPORTS = [
     's3_bc_base_series', 's3_bc_moments', 's3_bc_window_quantiles',
     's3_bc_match_zero_rate', 's3_bc_presrat',
     's3_sample_gather', 's3_cc_night_mask', 's3_cc_window_gather',
-    's3_nn_fill',
+    's3_nn_fill', 's3_channel_moments', 's3_normalize_channels',
     's3_st_interp', 's3_resize2d', 's3_surface_downscale',
     's3_chunk_epilogue', 's3_chunk_time_last', 's3_chunk_time_first',
     's3_step_handover', 's3_broadcast_axis', 's3_branch_join',
@@ -272,6 +272,9 @@ def lib():
                                       C.POINTER(i32), i32, i32, i32, i32,
                                       C.POINTER(i32), i32, vp, vp]),
         's3_nn_fill': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+        's3_channel_moments': (i32, [vp, vp, i64, i32, vp]),
+        's3_normalize_channels': (i32, [vp, vp, i64, i32, pf, pf,
+                                        C.POINTER(C.c_ubyte)]),
         's3_bias_correct': (i32, [vp, vp, i32, i32, i32, i32, i32,
                                   C.POINTER(BiasChannel), i32, i32,
                                   C.POINTER(i32), vp, vp, vp,
@@ -365,6 +368,8 @@ TC_METHODS = {'subsample': 0, 'average': 1, 'total': 2, 'max': 3, 'min': 4}
 CM_SUBFILTER, CM_LINEAR, CM_MOM1, CM_SQUARE = 1, 2, 4, 8
 # s3_sample_gather: samples per launch, channels kept (include/sup3r_hip.h)
 SAMPLE_MAX_ORIGINS, SAMPLE_MAX_CHANNELS = 64, 32
+# s3_channel_moments / s3_normalize_channels: channels of a cube
+STATS_MAX_CHANNELS = 64
 # DualSamplerCC's status words and the fill's largest extent (include/sup3r_hip.h)
 CC_STATUS_WORDS = 4
 CC_NIGHT_MASK, CC_START_RAW, CC_START, CC_FILLED = 0, 1, 2, 3

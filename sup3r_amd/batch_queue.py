@@ -33,6 +33,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from .samplers import DeviceSampler
 from .utilities import Timer
 
 logger = logging.getLogger(__name__)
@@ -374,20 +375,86 @@ class DeviceBatchQueue:
         return (self.batch_size,) + lr, (self.batch_size,) + hr
 
 
+_NOT_KWARGS = ('self', 'samplers', 'train_samplers', 'val_samplers', 'means',
+               'stds', 'thread_name')
+
+
+def _init_parameters(cls):
+    """named parameters of ``cls.__init__`` and, while an ``__init__`` takes
+    ``**kwargs``, of the next ``__init__`` up the MRO it hands them on to"""
+    import inspect
+    params = {}
+    for base in cls.__mro__:
+        init = base.__dict__.get('__init__')
+        if init is None:
+            continue
+        hands_on = False
+        for p in inspect.signature(init).parameters.values():
+            if p.kind == p.VAR_KEYWORD:
+                hands_on = True
+            elif p.kind != p.VAR_POSITIONAL:
+                params.setdefault(p.name, p)
+        if not hands_on:
+            break
+    return params
+
+
+def _data_keywords(sampler_cls):
+    """the data keywords of a sampler class — its constructor's parameters up
+    to ``sample_shape`` — and the optional ``obs``"""
+    names = [n for n in _init_parameters(sampler_cls) if n != 'self']
+    required = names[:names.index('sample_shape')]
+    return required, [n for n in ('obs',) if n in names]
+
+
+def _signature_names(cls):
+    """keywords that ``cls(...)`` takes from a handler's ``**kwargs``"""
+    skip = set(_NOT_KWARGS)
+    if 'sample_shape' in _init_parameters(cls):          # a sampler class
+        required, optional = _data_keywords(cls)
+        skip.update(required, optional)
+    return {n for n in _init_parameters(cls) if n not in skip}
+
+
+def _container_kwargs(container, sampler_cls):
+    """a container's data as the keywords of ``sampler_cls``: a mapping's
+    items, or an object's attributes (``data`` of an object with
+    ``as_array()`` is what that returns)"""
+    from collections.abc import Mapping
+    required, optional = _data_keywords(sampler_cls)
+
+    def value(key):
+        if isinstance(container, Mapping):
+            return container[key]
+        if key == 'data' and callable(getattr(container, 'as_array', None)):
+            return container.as_array()
+        return getattr(container, key)
+    out = {k: value(k) for k in required}
+    for k in optional:
+        if (k in container if isinstance(container, Mapping)
+                else getattr(container, k, None) is not None):
+            out[k] = value(k)
+    return out
+
+
 class DeviceBatchHandler(DeviceBatchQueue):
     """Training queue + validation queue + normalisation stats: the object
     ``Sup3rGan.train`` consumes (``BatchHandlerFactory``,
     sup3r/preprocessing/batch_handlers/factory.py:33-310).  The reference
-    builds its samplers from data containers; here ready samplers are handed
-    in (duck-typed, see the module docstring) and ``means`` / ``stds`` are the
-    per-feature dicts the model stores for ``norm_input`` / ``un_norm_output``
-    (``StatsCollection`` is part of the data layer).
+    builds its samplers from data containers and normalises them with a
+    ``StatsCollection``: that constructor is :meth:`from_containers`.  This
+    one takes ready samplers (duck-typed, see the module docstring) and
+    ``means`` / ``stds``, the per-feature dicts the model stores for
+    ``norm_input`` / ``un_norm_output``; it computes nothing and, given none,
+    records 0 and 1.
 
     ``VAL_QUEUE`` is the class of the validation queue; a handler of another
     queue class (batch_queue_conditional.py) names that class here and lists
-    it as a base behind this one, ``queue_kwargs`` then reach both queues."""
+    it as a base behind this one, ``queue_kwargs`` then reach both queues.
+    ``SAMPLER`` is the sampler class :meth:`from_containers` builds."""
 
     VAL_QUEUE = DeviceBatchQueue
+    SAMPLER = DeviceSampler
 
     def __init__(self, train_samplers, val_samplers=None, batch_size=16,
                  n_batches=64, s_enhance=1, t_enhance=1, means=None, stds=None,
@@ -407,6 +474,64 @@ class DeviceBatchHandler(DeviceBatchQueue):
             else dict(means)
         self.stds = {f: np.float32(1.0) for f in feats} if stds is None \
             else dict(stds)
+
+    # ------------------------------------------- the reference's constructor
+    @classmethod
+    def from_containers(cls, train_containers, val_containers=None,
+                        sample_shape=None, batch_size=16, n_batches=64,
+                        s_enhance=1, t_enhance=1, means=None, stds=None,
+                        queue_cap=None, transform_kwargs=None, max_workers=1,
+                        mode='lazy', feature_sets=None, **kwargs):
+        """The reference's handler constructor (batch_handlers/factory.py:
+        183-251) with arrays in the place of files: build a ``cls.SAMPLER``
+        per container, compute the missing ``means`` / ``stds`` over the
+        training samplers (:class:`~sup3r_amd.stats.DeviceStatsCollection`: a
+        dict, a JSON path or None each), normalise training and validation
+        samplers IN PLACE, and construct the handler with those stats.
+
+        A container is a mapping of the sampler's data keywords, or an object
+        with those attributes: ``data`` + ``features`` (an object with
+        ``as_array()``, a ``DeviceDeriver``, gives ``data`` through it);
+        ``low_res`` + ``high_res`` + ``lr_features`` + ``hr_features``
+        [+ ``obs``]; ``daily`` + ``hourly`` + ...  A cube that is a
+        contiguous fp32 device tensor is not copied: the caller's memory is
+        normalised.  ``kwargs`` go to the sampler and the two queues by their
+        signatures; one that nobody takes is an ``AssertionError``."""
+        from .stats import DeviceStatsCollection
+        add_kwargs = {'s_enhance': s_enhance, 't_enhance': t_enhance, **kwargs}
+        sampler_names = _signature_names(cls.SAMPLER)
+        sampler_kwargs = {k: v for k, v in add_kwargs.items()
+                          if k in sampler_names}
+        val_kwargs = {k: v for k, v in add_kwargs.items()
+                      if k in _signature_names(cls.VAL_QUEUE)}
+        main_kwargs = {k: v for k, v in add_kwargs.items()
+                       if k in _signature_names(cls)}
+        bad_kwargs = (set(kwargs) - set(sampler_kwargs) - set(val_kwargs)
+                      - set(main_kwargs))
+        assert not bad_kwargs, (f'{cls.__name__} received bad '
+                                f'kwargs = {bad_kwargs}.')
+
+        def samplers(containers):
+            return [cls.SAMPLER(
+                **_container_kwargs(c, cls.SAMPLER), sample_shape=sample_shape,
+                batch_size=batch_size, feature_sets=feature_sets,
+                **sampler_kwargs) for c in containers or []]
+        train_samplers = samplers(train_containers)
+        val_samplers = samplers(val_containers)
+        logger.info('Normalizing training samplers')
+        stats = DeviceStatsCollection(train_samplers, means=means, stds=stds)
+        if val_samplers:
+            logger.info('Normalizing validation samplers.')
+            stats.normalize(val_samplers)
+        queue_kwargs = {**val_kwargs, **main_kwargs}
+        for k in ('s_enhance', 't_enhance'):
+            queue_kwargs.pop(k, None)
+        return cls(train_samplers, val_samplers or None,
+                   batch_size=batch_size, n_batches=n_batches,
+                   s_enhance=s_enhance, t_enhance=t_enhance, means=stats.means,
+                   stds=stats.stds, queue_cap=queue_cap,
+                   transform_kwargs=transform_kwargs, max_workers=max_workers,
+                   mode=mode, **queue_kwargs)
 
     @property
     def smoothing(self):

@@ -19,6 +19,7 @@ reference (models/dc.py:59-60) and here.
 import numpy as np
 
 from .batch_queue import DeviceBatchHandler, DeviceBatchQueue, _as_arrays
+from .samplers import DeviceSamplerDC
 
 
 class DeviceBatchQueueDC(DeviceBatchQueue):
@@ -92,6 +93,7 @@ class DeviceBatchHandlerDC(DeviceBatchHandler, DeviceBatchQueueDC):
     must be at least as many box starts / time starts as bins."""
 
     VAL_QUEUE = DeviceValBatchQueueDC
+    SAMPLER = DeviceSamplerDC
 
     def __init__(self, train_samplers, val_samplers, **kwargs):
         assert val_samplers is not None and val_samplers != [], (

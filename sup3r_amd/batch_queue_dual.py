@@ -22,6 +22,8 @@ import ctypes as C
 import numpy as np
 
 from .batch_queue import DeviceBatchHandler, DeviceBatchQueue
+from .samplers import DeviceDualSampler
+from .samplers_cc import DeviceDualSamplerCC
 
 
 class DeviceDualBatchQueue(DeviceBatchQueue):
@@ -91,6 +93,7 @@ class DeviceDualBatchHandler(DeviceBatchHandler, DeviceDualBatchQueue):
     :class:`DeviceDualBatchQueue` + means / stds."""
 
     VAL_QUEUE = DeviceDualBatchQueue
+    SAMPLER = DeviceDualSampler
 
 
 class DeviceBatchHandlerCC(DeviceDualBatchHandler):
@@ -99,6 +102,8 @@ class DeviceBatchHandlerCC(DeviceDualBatchHandler):
     over :class:`~sup3r_amd.samplers_cc.DeviceDualSamplerCC` samplers, which
     hand out daily low-res / hourly high-res batches with the clearsky ratio
     reduced to daylight and filled — what ``SolarCC`` trains on."""
+
+    SAMPLER = DeviceDualSamplerCC
 
 
 # the reference's names

@@ -34,6 +34,12 @@ per process, on ``Device.get()`` of that rank) and draws with its own seed.
 ``DualSamplerCC`` (daily / hourly pairs, daylight reduction and ``nn_fill`` of
 the clearsky ratio) is in samplers_cc.py.  Not here: reading containers from
 files.
+
+Statistics: ``sampler.channel_moments(names)`` (one ``s3_channel_moments`` pass
+per cube, cached) and ``sampler.normalize(means, stds)`` (``s3_normalize_
+channels``, in place) are what :class:`~sup3r_amd.stats.DeviceStatsCollection`
+drives — the stage the reference runs between building its samplers and
+starting its queues.
 """
 import ctypes as C
 import logging
@@ -68,10 +74,44 @@ def sample_gather(dev, cube, origins, box, channels):
     return out
 
 
+def channel_moments(dev, cube):
+    """``(C, 3)`` float64 — count of non-NaN values, their mean, their sum of
+    squared deviations from it — per channel of the channels-last fp32 device
+    tensor ``cube``: one ``s3_channel_moments`` pass and one read-back."""
+    import torch
+    from . import _lib
+    c = int(cube.shape[-1])
+    out = torch.empty((c, 3), dtype=torch.float64, device=cube.device)
+    rc = _lib.lib().s3_channel_moments(
+        dev.ctx, C.c_void_p(cube.data_ptr()), cube.numel() // c, c,
+        C.c_void_p(out.data_ptr()))
+    _lib.check(rc, dev.ctx, 's3_channel_moments')
+    return out.cpu().numpy()
+
+
+def normalize_channels(dev, cube, means, stds, flags):
+    """``cube[..., q] = (cube[..., q] - means[q]) / stds[q]`` in place where
+    ``flags[q]``: one asynchronous ``s3_normalize_channels`` (float32, two
+    correctly rounded operations)."""
+    from . import _lib
+    c = int(cube.shape[-1])
+    m = np.ascontiguousarray(means, dtype=np.float32)
+    s = np.ascontiguousarray(stds, dtype=np.float32)
+    f = np.ascontiguousarray(flags, dtype=np.uint8)
+    assert len(m) == len(s) == len(f) == c, (len(m), len(s), len(f), c)
+    pf = C.POINTER(C.c_float)
+    rc = _lib.lib().s3_normalize_channels(
+        dev.ctx, C.c_void_p(cube.data_ptr()), cube.numel() // c, c,
+        m.ctypes.data_as(pf), s.ctypes.data_as(pf),
+        f.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    _lib.check(rc, dev.ctx, 's3_normalize_channels')
+
+
 class _ResidentCube:
     """one ``(S1, S2, T, C)`` cube and the names of its channels: on the device
     (fp32, contiguous, uploaded here once), or — with a stand-in gather — just
-    its shape"""
+    its shape.  ``Device.to_device`` does not copy a contiguous fp32 device
+    tensor: a cube handed in as one is normalised in the caller's memory."""
 
     def __init__(self, data, features, device, gather, what):
         self.features = list(features)
@@ -82,6 +122,7 @@ class _ResidentCube:
         self.shape = shape
         self._index = {f.lower(): i for i, f in enumerate(self.features)}
         self.dev, self.tensor, self._gather = device, None, gather
+        self._moments = None
         if gather is None:
             from . import _lib
             from .engine import Device
@@ -103,6 +144,55 @@ class _ResidentCube:
             raise ValueError(f'a sample carries at most {self.max_channels} '
                              f'features, {len(channels)} were asked for')
         return sample_gather(self.dev, self.tensor, origins, box, channels)
+
+    def _need_tensor(self, what):
+        if self.tensor is None:
+            raise RuntimeError(f'{what} needs the cube on the device; this '
+                               'one stands in for it with a gather callable')
+
+    def moments(self, names):
+        """``{name: (count, mean, std)}`` over all of space and time, NaN
+        skipped, ddof 0 (xarray's ``.mean(skipna=True)`` / ``.std(skipna=
+        True)``): one ``s3_channel_moments`` pass over the whole cube and one
+        read-back of ``3 C`` doubles, kept until :meth:`normalize` changes the
+        data.  A feature without a value is NaN, with a warning."""
+        idx = self.channels(names)
+        if self._moments is None:
+            self._need_tensor('moments()')
+            self._moments = channel_moments(self.dev, self.tensor)
+        out = {}
+        for name, i in zip(names, idx):
+            n, mean, m2 = self._moments[i]
+            if n == 0:
+                msg = (f'feature "{name}" holds no value (all NaN): its mean '
+                       'and standard deviation are NaN')
+                logger.warning(msg)
+                warn(msg)
+                out[name] = (0, np.float64('nan'), np.float64('nan'))
+            else:
+                with np.errstate(invalid='ignore'):
+                    out[name] = (int(n), np.float64(mean),
+                                 np.sqrt(np.float64(m2) / np.float64(n)))
+        return out
+
+    def normalize(self, means, stds):
+        """``x = (x - float32(mean)) / float32(std)`` IN PLACE for the
+        features present in both dicts (``Sup3rX.normalize``,
+        accessor.py:356-361; names compared in lower case): one
+        ``s3_normalize_channels`` pass, bit for bit numpy's float32 result."""
+        lo_m = {str(k).lower(): v for k, v in means.items()}
+        lo_s = {str(k).lower(): v for k, v in stds.items()}
+        c = len(self.features)
+        m, s = np.zeros(c, np.float32), np.ones(c, np.float32)
+        flag = np.zeros(c, np.uint8)
+        for i, f in enumerate(self.features):
+            if f.lower() in lo_m and f.lower() in lo_s:
+                m[i], s[i], flag[i] = lo_m[f.lower()], lo_s[f.lower()], 1
+        if not flag.any():
+            return
+        self._need_tensor('normalize()')
+        normalize_channels(self.dev, self.tensor, m, s, flag)
+        self._moments = None
 
 
 class DeviceSampler:
@@ -151,6 +241,20 @@ class DeviceSampler:
     def compute(self):
         """nothing to load: the data is already on the device"""
         return self
+
+    # ----------------------------------------------------------- statistics
+    def channel_moments(self, names):
+        """``{name: (count, mean, std)}`` of the named features over the whole
+        cube (NaN skipped, ddof 0, float64): what ``StatsCollection`` asks of
+        a container.  One pass and one read-back per cube, cached."""
+        return self._cube.moments(list(names))
+
+    def normalize(self, means, stds):
+        """normalise the cube IN PLACE with the features found in both dicts.
+        A cube handed to the constructor as a contiguous fp32 device tensor
+        was not copied: it is the caller's memory that is normalised, as the
+        reference normalises its containers' datasets."""
+        self._cube.normalize(means, stds)
 
     @property
     def sample_shape(self):
@@ -422,6 +526,38 @@ class DeviceDualSampler(DeviceSampler):
     def obs(self):
         return None if self._obs is None else self._obs.tensor
 
+    def _members(self):
+        return [c for c in (self._lr, self._hr, self._obs) if c is not None]
+
+    def channel_moments(self, names):
+        """the split of ``StatsCollection._get_stat`` (collections/stats.py:
+        51-74): features that ``high_res`` carries come from ``high_res``, the
+        remaining ones from ``low_res``; ``obs`` is never asked"""
+        names = list(names)
+        hr_names = _lowered(self._hr.features)
+        hr = [f for f in names if f.lower() in hr_names]
+        out = self._hr.moments(hr) if hr else {}
+        lr = [f for f in names if f.lower() not in hr_names]
+        if lr:
+            out.update(self._lr.moments(lr))
+        return {f: out[f] for f in names}
+
+    def normalize(self, means, stds):
+        """every member — ``low_res``, ``high_res`` and ``obs`` — IN PLACE,
+        each for its features found in both dicts (``Sup3rX.normalize`` per
+        member).  Members that are one and the same device tensor (handed in
+        twice, not copied) are normalised once.  As for
+        :meth:`DeviceSampler.normalize`, cubes handed in as contiguous fp32
+        device tensors are the caller's memory."""
+        done = set()
+        for cube in self._members():
+            tensor = getattr(cube, 'tensor', None)
+            key = id(cube) if tensor is None else tensor.data_ptr()
+            if key not in done:
+                cube.normalize(means, stds)
+                done.add(key)
+            cube._moments = None
+
     def get_sample_index(self, n_obs=None):
         """``(lr_index, hr_index[, obs_index])``: drawn on the low-res grid,
         the hi-res box is that box times the enhancement factors"""
@@ -462,5 +598,5 @@ Sampler, SamplerDC, DualSampler = DeviceSampler, DeviceSamplerDC, \
     DeviceDualSampler
 
 __all__ = ['DeviceSampler', 'DeviceSamplerDC', 'DeviceDualSampler',
-           'start_probabilities', 'sample_gather', 'Sampler', 'SamplerDC',
-           'DualSampler']
+           'start_probabilities', 'sample_gather', 'channel_moments',
+           'normalize_channels', 'Sampler', 'SamplerDC', 'DualSampler']
