@@ -1224,6 +1224,84 @@ int s3_range_mask(s3_ctx* ctx, const float* data, int c, int ch, int64_t n_pos,
 int s3_fill_indexed(s3_ctx* ctx, float* data, int c, int ch, int64_t n_pos,
                     const unsigned char* mask, const int* src);
 
+/* ---- QA of a forward pass on the device --------------------
+ * replaces the host numpy of Sup3rQa.run (sup3r/qa/qa.py:467-514) and of the
+ * distributions and spectra of sup3r/qa/utilities.py.
+ *
+ * s3_qa_recoarsen: the high-resolution field re-coarsened onto the source grid
+ *   (get_dset_out -> spatial_coarsening(obs_axis=False) -> temporal_coarsening,
+ *   qa.py:296-374), the error against the source and its summary, one read of
+ *   the field.  hr is S3_QA_CUBE (H1, H2, HT, C) with channel_host[f] the
+ *   channel of feature f, or S3_QA_TIME_FIRST (HT, H1, H2) (C = F = 1,
+ *   channel_host unused).  method_host[f] is S3_TC_*.  true_host / syn_host /
+ *   err_host are host arrays of F device pointers to planar (S1, S2, T) fp32
+ *   fields (S = H / s_enhance, T = HT / t_enhance): syn = the re-coarsened
+ *   field, err = syn - true.  Any of the three arrays, or an entry of syn_host /
+ *   err_host, may be NULL; err and the summary need true.
+ *   Arithmetic, separately rounded fp32 in this order (tests/qa_ref.py): per
+ *   step the s row sums over j, their sum over i, a true division by
+ *   float(s^2); then over the t_enhance steps: SUBSAMPLE step 0, TOTAL a sum
+ *   with NaN as +0, AVERAGE that sum / float(t_enhance), MAX / MIN hand NaN on.
+ *   summary (device, F x S3_QA_SUMMARY_WORDS doubles, or NULL): over the finite
+ *   errors of feature f the count, sum e, sum |e|, sum e^2 and max |e|, the
+ *   sums in fp64 folded in a fixed order (no float atomics: two runs give equal
+ *   bits).  Offsets are 64-bit.
+ *   S3_EINVAL, before anything is launched: s_enhance not dividing H1 or H2,
+ *   t_enhance not dividing HT, an unknown method or layout, F outside 1 ..
+ *   S3_QA_MAX_FEATURES, a channel outside the cube, t_enhance * C above 4096
+ *   (cube), s_enhance above 64 or a t_enhance whose tile exceeds a workgroup's
+ *   LDS (time-first).
+ *
+ * The distributions (direct_dist, gradient_dist, time_derivative_dist,
+ * utilities.py:170-342) never store the transformed value d: element e of it is
+ *   diff == 0:  x = v[e];  has_period: x = (x + period) % period
+ *   diff != 0:  x = v[src + delta] - v[src], src = (e / inner_out) inner_in +
+ *               e % inner_out (np.diff(axis=1): inner_out = (s2 - 1) t,
+ *               inner_in = s2 t, delta = t; v[..., k:] - v[..., :-k]: t - k, t,
+ *               k);  has_period: x = (x + half_period) % period - half_period
+ *   d = x / scale
+ * in numpy's float32 operations (`%` with the divisor's sign).  n = the number
+ * of values of d, at most 2^31 - 1 (S3_EINVAL above).
+ * s3_qa_select: the order statistics rank0 <= rank1 (0-based) of |d| by a radix
+ *   select over its bit patterns, four passes of 8 bits, per-workgroup
+ *   histograms in LDS, integer atomics; out (device, 4 words) = bits of the two
+ *   values, the NaN count (NaN sorts last, as in numpy), 0.
+ * s3_qa_hist: over the kept values (|d| < diff_max, or all that are not NaN
+ *   with S3_QA_HIST_KEEP_ALL) S3_QA_HIST_STATS writes stats (device, 5
+ *   doubles) = count, sum d^2 (fp64, fixed order), min, max, NaN count (the
+ *   NaN count is always written); S3_QA_HIST_COUNTS writes counts[n_bins]
+ *   (uint32, zeroed here) = np.histogram's over uniform bins: values outside
+ *   [first_edge, last_edge] dropped, the scaled index ((d - first_edge) / denom)
+ *   * n_bins in fp32, or from the division on in fp64 if `wide` (numpy's
+ *   arithmetic when `range` is given), then the decrement / increment against
+ *   edges (device, n_bins + 1 floats, numpy's), the last edge inclusive.
+ *   n_bins <= S3_QA_MAX_BINS.
+ * s3_qa_power_sum: out[l] (device, L doubles) = sum over (o, i) of re^2 + im^2
+ *   of an (outer, L, inner) view, of both fields if re1 / im1 are given; fp64,
+ *   fixed order.  By Parseval the mean over one axis of |fftn|^2 is this sum
+ *   over the 1-D transform along the other axis (s3_dft_axis). */
+#define S3_QA_CUBE 0
+#define S3_QA_TIME_FIRST 1
+#define S3_QA_MAX_FEATURES 16
+#define S3_QA_SUMMARY_WORDS 5
+#define S3_QA_MAX_BINS 4096
+#define S3_QA_HIST_STATS 1
+#define S3_QA_HIST_COUNTS 2
+#define S3_QA_HIST_KEEP_ALL 4
+int s3_qa_recoarsen(s3_ctx* ctx, const float* hr, int layout, int64_t H1, int64_t H2, int64_t HT, int C,
+                    const int* channel_host, const int* method_host, int F, int s_enhance, int t_enhance,
+                    const float* const* true_host, float* const* syn_host, float* const* err_host,
+                    double* summary);
+int s3_qa_select(s3_ctx* ctx, const float* v, int diff, int64_t n, int64_t inner_out, int64_t inner_in,
+                 int64_t delta, int has_period, float period, float half_period, float scale,
+                 int64_t rank0, int64_t rank1, uint32_t* out);
+int s3_qa_hist(s3_ctx* ctx, const float* v, int diff, int64_t n, int64_t inner_out, int64_t inner_in,
+               int64_t delta, int has_period, float period, float half_period, float scale, int flags,
+               float diff_max, float first_edge, float last_edge, double denom, int wide, int n_bins,
+               const float* edges, uint32_t* counts, double* stats);
+int s3_qa_power_sum(s3_ctx* ctx, const float* re0, const float* im0, const float* re1, const float* im1,
+                    int64_t outer, int L, int64_t inner, double* out);
+
 /* ---- data-parallel gradient sync (RCCL over xGMI) -----------------------
  * replaces: the host-side python sum of per-GPU gradient lists,
  * AbstractSingleModel._sum_parallel_grad (abstract.py:785-805): elementwise

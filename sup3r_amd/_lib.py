@@ -59,6 +59,7 @@ EXPORTS = [
     's3_stack_features', 's3_level_stats',
     's3_exo_nearest_work_bytes', 's3_exo_nearest',
     's3_exo_group_mean_work_bytes', 's3_exo_group_mean',
+    's3_qa_recoarsen', 's3_qa_select', 's3_qa_hist', 's3_qa_power_sum',
     's3_comm_unique_id', 's3_comm_init', 's3_params_allreduce_grads',
     's3_params_arm_allreduce',
     's3_allreduce_sum', 's3_params_broadcast', 's3_broadcast',
@@ -246,6 +247,16 @@ def lib():
         's3_exo_group_mean': (i32, [vp, vp, vp, i64, i64, i64, i64,
                                     C.POINTER(i32), C.c_double, vp, i64, vp,
                                     vp]),
+        's3_qa_recoarsen': (i32, [vp, vp, i32, i64, i64, i64, i32,
+                                  C.POINTER(i32), C.POINTER(i32), i32, i32,
+                                  i32, C.POINTER(vp), C.POINTER(vp),
+                                  C.POINTER(vp), vp]),
+        's3_qa_select': (i32, [vp, vp, i32, i64, i64, i64, i64, i32, f32, f32,
+                               f32, i64, i64, vp]),
+        's3_qa_hist': (i32, [vp, vp, i32, i64, i64, i64, i64, i32, f32, f32,
+                             f32, i32, f32, f32, f32, C.c_double, i32, i32,
+                             vp, vp, vp]),
+        's3_qa_power_sum': (i32, [vp, vp, vp, vp, vp, i64, i32, i64, vp]),
         's3_host_register': (i32, [vp, vp, C.c_size_t]),
         's3_host_unregister': (i32, [vp, vp]),
         's3_d2h_window': (i32, [vp, vp, vp, i64, i64, i64, i64, i64, vp]),
@@ -400,6 +411,10 @@ LS_WORDS = 8
  LS_LAST_MAX, LS_LAST_MIN) = range(8)
 # s3_exo_group_mean: most columns of one slab (include/sup3r_hip.h)
 EXO_MAX_SLAB = 32
+# s3_qa_*: layouts, limits, the summary's words, flags (include/sup3r_hip.h)
+QA_CUBE, QA_TIME_FIRST = 0, 1
+QA_MAX_FEATURES, QA_SUMMARY_WORDS, QA_MAX_BINS = 16, 5, 4096
+QA_HIST_STATS, QA_HIST_COUNTS, QA_HIST_KEEP_ALL = 1, 2, 4
 
 
 def last_error(ctx):
