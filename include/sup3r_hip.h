@@ -1302,6 +1302,63 @@ int s3_qa_hist(s3_ctx* ctx, const float* v, int diff, int64_t n, int64_t inner_o
 int s3_qa_power_sum(s3_ctx* ctx, const float* re0, const float* im0, const float* re1, const float* im1,
                     int64_t outer, int L, int64_t inner, double* out);
 
+/* ---- the data handlers on the device -----------------------
+ * replaces the xarray / numpy of Rasterizer.rasterize_data,
+ * DailyDataHandler._deriver_hook and DataHandlerNCforCC.get_clearsky_ghi /
+ * scale_clearsky_ghi (sup3r/preprocessing/rasterizers/base.py, extended.py,
+ * data_handlers/base.py, nc_cc.py).  All four are asynchronous on the
+ * context's stream, use 64-bit element offsets and no float atomics.
+ *
+ * s3_raster_gather: n_planes <= S3_STACK_MAX_PLANES planes per launch, src_host
+ *   / out_host host arrays of device pointers; out is (n_i, n_j, n_k [, n_lev])
+ *   fp32, t-contiguous; every bit pattern is copied as it is.
+ *   S3_RG_GRID     src (src_s1, src_s2, src_t [, n_lev]):
+ *                  out[i, j, k, l] = src[r0 + i, c0 + j, t0 + k step, l]
+ *                  (a 2-D plane: src_t = n_k = 1, t0 = 0)
+ *   S3_RG_FLAT     src (src_t, src_s2 sites), site (device, n_i n_j int32):
+ *                  out[i, j, k] = src[t0 + k step, site[i n_j + j]]
+ *                  (src_s1 = n_lev = 1)
+ *   S3_RG_FLAT_1D  src (src_s2 sites): out[i, j] = src[site[i n_j + j]]
+ *                  (n_k = 1)
+ *   A cell whose site lies outside [0, src_s2) gets zero bits.  S3_EINVAL,
+ *   before anything is launched: a window or a step outside the source.
+ * s3_daily_reduce: sources (n_pix, n_days w), outputs (n_pix, n_days); output o
+ *   is op out_op_host[o] of the non-NaN values of each window of source
+ *   out_src_host[o].  Sums are fp64 in step order, rounded to fp32 once;
+ *   S3_DAILY_MEAN divides in fp64 by the count (0 / 0 = NaN), then rounds;
+ *   MAX / MIN are the element itself (NaN for a window of NaNs); SUM of such a
+ *   window is 0; S3_DAILY_RATIO is the fp32 quotient of the fp32-rounded sums
+ *   of the sources out_src_host[o] and out_src2_host[o].  A source is read once
+ *   per launch.  n_src <= S3_DAILY_MAX_SRC, n_out <= S3_DAILY_MAX_OUT, w < 8192.
+ * s3_site_day_mean: src (t_src, n_sites), idx (device, n_pix x k int32),
+ *   day_map (device, d_out int32): out[p, d] = NaN where day_map[d] < 0 or the
+ *   day lies behind the source's last whole day; else the mean over the m
+ *   steps t_lo + day_map[d] m + s of (the mean over the k sites, NaN skipped),
+ *   NaN skipped; fp64 throughout, one rounding.
+ * s3_scale_to_time_max: scale[p] = nanmax_t a[p, :] / nanmax_t b[p, :] (one
+ *   fp32 division), then b[p, :] *= scale[p] in place; a is only read. */
+#define S3_RG_GRID 0
+#define S3_RG_FLAT 1
+#define S3_RG_FLAT_1D 2
+#define S3_DAILY_MAX_SRC 8
+#define S3_DAILY_MAX_OUT 16
+#define S3_DAILY_MEAN 0
+#define S3_DAILY_MAX 1
+#define S3_DAILY_MIN 2
+#define S3_DAILY_SUM 3
+#define S3_DAILY_RATIO 4
+int s3_raster_gather(s3_ctx* ctx, int layout, int n_planes, const float* const* src_host,
+                     float* const* out_host, int64_t n_i, int64_t n_j, int64_t n_k, int64_t n_lev,
+                     int64_t src_s1, int64_t src_s2, int64_t src_t, int64_t r0, int64_t c0, int64_t t0,
+                     int64_t step, const int32_t* site);
+int s3_daily_reduce(s3_ctx* ctx, int n_src, const float* const* src_host, int64_t n_pix, int64_t n_days,
+                    int w, int n_out, const int* out_src_host, const int* out_src2_host,
+                    const int* out_op_host, float* const* out_host);
+int s3_site_day_mean(s3_ctx* ctx, const float* src, int64_t t_src, int64_t n_sites, const int32_t* idx,
+                     int64_t n_pix, int k, int64_t t_lo, int m, const int32_t* day_map, int64_t d_out,
+                     float* out);
+int s3_scale_to_time_max(s3_ctx* ctx, const float* a, float* b, int64_t n_pix, int64_t t, float* scale);
+
 /* ---- data-parallel gradient sync (RCCL over xGMI) -----------------------
  * replaces: the host-side python sum of per-GPU gradient lists,
  * AbstractSingleModel._sum_parallel_grad (abstract.py:785-805): elementwise

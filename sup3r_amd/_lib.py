@@ -60,6 +60,8 @@ EXPORTS = [
     's3_exo_nearest_work_bytes', 's3_exo_nearest',
     's3_exo_group_mean_work_bytes', 's3_exo_group_mean',
     's3_qa_recoarsen', 's3_qa_select', 's3_qa_hist', 's3_qa_power_sum',
+    's3_raster_gather', 's3_daily_reduce', 's3_site_day_mean',
+    's3_scale_to_time_max',
     's3_comm_unique_id', 's3_comm_init', 's3_params_allreduce_grads',
     's3_params_arm_allreduce',
     's3_allreduce_sum', 's3_params_broadcast', 's3_broadcast',
@@ -257,6 +259,15 @@ def lib():
                              f32, i32, f32, f32, f32, C.c_double, i32, i32,
                              vp, vp, vp]),
         's3_qa_power_sum': (i32, [vp, vp, vp, vp, vp, i64, i32, i64, vp]),
+        's3_raster_gather': (i32, [vp, i32, i32, C.POINTER(vp), C.POINTER(vp),
+                                   i64, i64, i64, i64, i64, i64, i64, i64,
+                                   i64, i64, i64, vp]),
+        's3_daily_reduce': (i32, [vp, i32, C.POINTER(vp), i64, i64, i32, i32,
+                                  C.POINTER(i32), C.POINTER(i32),
+                                  C.POINTER(i32), C.POINTER(vp)]),
+        's3_site_day_mean': (i32, [vp, vp, i64, i64, vp, i64, i32, i64, i32,
+                                   vp, i64, vp]),
+        's3_scale_to_time_max': (i32, [vp, vp, vp, i64, i64, vp]),
         's3_host_register': (i32, [vp, vp, C.c_size_t]),
         's3_host_unregister': (i32, [vp, vp]),
         's3_d2h_window': (i32, [vp, vp, vp, i64, i64, i64, i64, i64, vp]),
@@ -415,6 +426,10 @@ EXO_MAX_SLAB = 32
 QA_CUBE, QA_TIME_FIRST = 0, 1
 QA_MAX_FEATURES, QA_SUMMARY_WORDS, QA_MAX_BINS = 16, 5, 4096
 QA_HIST_STATS, QA_HIST_COUNTS, QA_HIST_KEEP_ALL = 1, 2, 4
+# s3_raster_gather / s3_daily_reduce: layouts, limits, ops (include/sup3r_hip.h)
+RG_GRID, RG_FLAT, RG_FLAT_1D = 0, 1, 2
+DAILY_MAX_SRC, DAILY_MAX_OUT = 8, 16
+DAILY_MEAN, DAILY_MAX, DAILY_MIN, DAILY_SUM, DAILY_RATIO = range(5)
 
 
 def last_error(ctx):

@@ -22,6 +22,9 @@ entry points (include/sup3r_hip.h, csrc/kernels_derive.hip):
     s3_stack_features    planes -> channels-last cube, ``time_roll`` fused
     s3_level_stats       the counts and extrema of ``run_level_check``
 
+(and four more for the data handlers, data_handlers.py over
+csrc/kernels_data_handler.hip: ``raster_gather``, ``daily_reduce``,
+``site_day_mean``, ``scale_to_time_max``).
 ``NumpyBackend`` is the same arithmetic restated in numpy, for testing the
 host control flow on a machine without a GPU; it is no fallback: nothing
 selects it but the caller.
@@ -360,6 +363,80 @@ class NumpyBackend:
         return np.ascontiguousarray(cube[..., i])
 
 
+    # -- the data handlers' operations (data_handlers.py)
+    DAILY_OPS = ('mean', 'max', 'min', 'sum', 'ratio')
+
+    def raster_gather(self, arrays, rows=None, cols=None, t0=0, step=1,
+                      n_k=1, site=None):
+        """``site`` None: ``a[rows, cols, t0 : : step][.., :n_k]`` of gridded
+        ``(s1, s2, t [, L])`` arrays (a 2-D array has no time axis); else the
+        raster ``site`` (n_i, n_j) of flat ``(t, sites)`` / ``(sites,)``
+        arrays as ``(n_i, n_j, n_k)`` / ``(n_i, n_j)``.  Bits are copied."""
+        steps = slice(t0, t0 + (n_k - 1) * step + 1, step)
+        out = []
+        for a in arrays:
+            a = np.asarray(a)
+            if site is None:
+                a = a[rows, cols] if a.ndim == 2 else a[rows, cols, steps]
+            elif a.ndim == 1:
+                a = a[site]
+            else:
+                a = np.moveaxis(a[steps][:, site], 0, -1)
+            out.append(np.ascontiguousarray(a))
+        return out
+
+    def daily_reduce(self, sources, w, outputs):
+        """``sources``: planes (s1, s2, D w); ``outputs``: (source, second
+        source | None, op in DAILY_OPS) each; returns planes (s1, s2, D).
+        xarray's ``coarsen(time=w).mean() / .max() / .min() / .sum()`` with
+        NaN skipped, in float64, rounded to float32 once; ``ratio`` is the
+        float32 quotient of the two float32 sums."""
+        wins = [np.asarray(a, np.float64).reshape(*a.shape[:2], -1, w)
+                for a in sources]
+        fn = {'mean': np.nanmean, 'max': np.nanmax, 'min': np.nanmin,
+              'sum': np.nansum}
+        out = []
+        with np.errstate(all='ignore'), warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            for i, j, op in outputs:
+                if op == 'ratio':
+                    a = np.nansum(wins[i], axis=-1).astype(np.float32)
+                    b = np.nansum(wins[j], axis=-1).astype(np.float32)
+                    out.append(a / b)
+                else:
+                    out.append(fn[op](wins[i], axis=-1).astype(np.float32))
+        return out
+
+    def site_day_mean(self, src, idx, t_lo, m, day_map):
+        """``src`` (t, sites), ``idx`` (n_pix, k), ``day_map`` (D,): ``out[p,
+        d]`` = NaN where ``day_map[d] < 0``, else the NaN-skipping mean over
+        the ``m`` steps of source day ``day_map[d]`` (counted from ``t_lo``)
+        of the NaN-skipping mean over the ``k`` sites; float64, one rounding"""
+        src = np.asarray(src, np.float64)
+        idx, day_map = np.asarray(idx), np.asarray(day_map)
+        n_days = (len(src) - t_lo) // m
+        with np.errstate(all='ignore'), warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            sites = np.nanmean(src[t_lo:t_lo + n_days * m][:, idx], axis=-1)
+            days = np.nanmean(sites.reshape(n_days, m, -1), axis=1)   # (d, p)
+        ok = (day_map >= 0) & (day_map < n_days)
+        out = np.full((idx.shape[0], len(day_map)), np.nan, np.float32)
+        out[:, ok] = days[day_map[ok]].T.astype(np.float32)
+        return out
+
+    def scale_to_time_max(self, a, b):
+        """``scale = nanmax_t a / nanmax_t b`` per pixel (float32), ``b *
+        scale``: returns ``(b scaled, scale)``"""
+        with np.errstate(all='ignore'), warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            scale = (np.nanmax(a, axis=-1) / np.nanmax(b, axis=-1)).astype(
+                np.float32)
+            return (b * scale[..., None]).astype(np.float32), scale
+
+    def to_index(self, x):
+        return np.ascontiguousarray(x, dtype=np.int32)
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -539,6 +616,136 @@ class DeviceBackend:
     def channel(self, cube, i):
         return cube[..., i].contiguous()
 
+
+    # -- the data handlers' kernels (csrc/kernels_data_handler.hip)
+    DAILY_OPS = NumpyBackend.DAILY_OPS
+
+    def to_index(self, x):
+        """an int32 table on the device"""
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(
+            self.dev.torch_device)
+
+    def _gather(self, layout, arrays, out_shape, n_k, n_lev, src, r0, c0, t0,
+                step, site):
+        n_i, n_j = out_shape[:2]
+        outs = []
+        for at in range(0, len(arrays), _lib.STACK_MAX_PLANES):
+            part = list(arrays[at:at + _lib.STACK_MAX_PLANES])
+            new = [self.dev.empty(out_shape) for _ in part]
+            self._call('s3_raster_gather', layout, len(part),
+                       self._pointers(part), self._pointers(new), n_i, n_j,
+                       n_k, n_lev, *src, r0, c0, t0, step, _ptr(site))
+            outs += new
+        return outs
+
+    def raster_gather(self, arrays, rows=None, cols=None, t0=0, step=1,
+                      n_k=1, site=None):
+        """as ``NumpyBackend.raster_gather``: arrays of one geometry share a
+        launch (``s3_raster_gather``)"""
+        arrays = [a.contiguous() for a in arrays]
+        out = [None] * len(arrays)
+        groups = {}
+        for i, a in enumerate(arrays):
+            groups.setdefault(tuple(a.shape), []).append(i)
+        if site is not None:
+            site_np = np.asarray(site)
+            n_i, n_j = site_np.shape
+            table = self.to_index(site_np.reshape(-1))
+        for shape, members in groups.items():
+            part = [arrays[i] for i in members]
+            if site is None:
+                r = range(*rows.indices(shape[0]))
+                c = range(*cols.indices(shape[1]))
+                assert r.step == 1 and c.step == 1 and len(r) and len(c)
+                flat2d = len(shape) == 2
+                n_lev = shape[3] if len(shape) == 4 else 1
+                o_shape = (len(r), len(c)) if flat2d else (
+                    (len(r), len(c), n_k) + ((n_lev,) if len(shape) == 4
+                                             else ()))
+                new = self._gather(
+                    _lib.RG_GRID, part, o_shape, 1 if flat2d else n_k, n_lev,
+                    (shape[0], shape[1], 1 if flat2d else shape[2]),
+                    r.start, c.start, 0 if flat2d else t0,
+                    1 if flat2d else step, None)
+            else:
+                if site_np.size and (site_np.min() < 0
+                                     or site_np.max() >= shape[-1]):
+                    raise IndexError(
+                        f'raster_index outside the {shape[-1]} sites')
+                if len(shape) == 1:
+                    new = self._gather(_lib.RG_FLAT_1D, part, (n_i, n_j), 1,
+                                       1, (1, shape[0], 1), 0, 0, 0, 1, table)
+                else:
+                    new = self._gather(_lib.RG_FLAT, part, (n_i, n_j, n_k),
+                                       n_k, 1, (1, shape[1], shape[0]), 0, 0,
+                                       t0, step, table)
+            for i, plane in zip(members, new):
+                out[i] = plane
+        return out
+
+    def daily_reduce(self, sources, w, outputs):
+        """as ``NumpyBackend.daily_reduce`` (``s3_daily_reduce``): one launch
+        while the tables hold the sources and outputs, else one per run of
+        outputs that fits"""
+        s1, s2, t = (int(v) for v in sources[0].shape)
+        assert t % w == 0, (t, w)
+        days = t // w
+        sources = [a.contiguous() for a in sources]
+        out = [self.dev.empty((s1, s2, days)) for _ in outputs]
+        ops = {name: i for i, name in enumerate(self.DAILY_OPS)}
+        launch, used = [], []
+
+        def flush():
+            if not launch:
+                return
+            slot = {s: i for i, s in enumerate(used)}
+            n = len(launch)
+            i32 = C.c_int32 * n
+            self._call(
+                's3_daily_reduce', len(used),
+                self._pointers([sources[s] for s in used]), s1 * s2, days,
+                int(w), n, i32(*[slot[outputs[o][0]] for o in launch]),
+                i32(*[slot.get(outputs[o][1], 0) for o in launch]),
+                i32(*[ops[outputs[o][2]] for o in launch]),
+                self._pointers([out[o] for o in launch]))
+            launch.clear()
+            used.clear()
+        for o, (i, j, op) in enumerate(outputs):
+            wanted = list(dict.fromkeys((i, j) if op == 'ratio' else (i,)))
+            need = [s for s in wanted if s not in used]
+            if (len(used) + len(need) > _lib.DAILY_MAX_SRC
+                    or len(launch) + 1 > _lib.DAILY_MAX_OUT):
+                flush()
+                need = wanted
+            used += need
+            launch.append(o)
+        flush()
+        return out
+
+    def site_day_mean(self, src, idx, t_lo, m, day_map):
+        """as ``NumpyBackend.site_day_mean`` (``s3_site_day_mean``)"""
+        src = src.contiguous()
+        idx = np.asarray(idx)
+        n_pix, k = idx.shape
+        out = self.dev.empty((n_pix, len(day_map)))
+        # (both tables stay referenced until the launch is enqueued: a freed
+        # block would be handed to the next allocation)
+        idx_d, map_d = self.to_index(idx), self.to_index(day_map)
+        self._call('s3_site_day_mean', _ptr(src), int(src.shape[0]),
+                   int(src.shape[1]), _ptr(idx_d), n_pix, k, int(t_lo),
+                   int(m), _ptr(map_d), len(day_map), _ptr(out))
+        return out
+
+    def scale_to_time_max(self, a, b):
+        """as ``NumpyBackend.scale_to_time_max``; ``b`` is scaled IN PLACE
+        when it is contiguous (``s3_scale_to_time_max``)"""
+        a, b = a.contiguous(), b.contiguous()
+        s1, s2, t = (int(v) for v in b.shape)
+        scale = self.dev.empty((s1, s2))
+        self._call('s3_scale_to_time_max', _ptr(a), _ptr(b), s1 * s2, t,
+                   _ptr(scale))
+        return b, scale
 
 # --------------------------------------------------------------- the dataset
 class DeriveData:
