@@ -125,7 +125,13 @@ enum { S3_STAT_PERSIST_DGRAD = 0, /* trunk data gradients on the persistent kern
        S3_STAT_AXPY = 25,           /* skip accumulation, one element per lane                  */
        S3_STAT_AXPY4 = 26,          /* skip accumulation, four elements per lane                */
        S3_STAT_PERSIST_SKIPPRE = 27, /* trunk convs whose skip rows load under the last taps   */
-       S3_STAT_COUNT = 28 };
+       /* in-family variants of the discriminator's conv kernels that s3_plan_op_info does not tell apart */
+       S3_STAT_HALO_S2_K64 = 28,    /* stride-2 LDS-halo forwards on the 64-channel split kernel */
+       S3_STAT_FEWCH_HALO = 29,     /* few-channel forwards on the LDS-halo kernel (not the gather walk) */
+       S3_STAT_FEWCH_HALO_SIGNS = 30, /* ... of those, the ones that wrote activation sign bytes   */
+       S3_STAT_DGRAD_S2_O16 = 31,   /* stride-2 data gradients that stored dx as bf16 only        */
+       S3_STAT_DGRAD_S2_MB = 32,    /* ... of those, the ones that masked from sign bytes         */
+       S3_STAT_COUNT = 33 };
 int64_t s3_ctx_stat(const s3_ctx* ctx, int which);
 
 /* ---- parameter store ---------------------------------------------------

@@ -350,7 +350,10 @@ STATS = {'persist_dgrad': 0, 'gconv_splitk': 1, 'bucket_elems': 2,
          'fold16x8': 21, 'fold_plain': 22, 'fold_masked': 23, 'fold_add': 24,
          'axpy': 25, 'axpy4': 26,
          # persistent trunk convs launched on the skip-prefetch variant
-         'persist_skippre': 27}
+         'persist_skippre': 27,
+         # in-family variants of the discriminator's conv kernels
+         'halo_s2_k64': 28, 'fewch_halo': 29, 'fewch_halo_signs': 30,
+         'dgrad_s2_o16': 31, 'dgrad_s2_mb': 32}
 
 
 def option_names():

@@ -387,5 +387,7 @@ int launch_conv_dgrad_s2(s3_ctx* ctx, const ConvGeom& g, const float* dy, const 
                        (const unsigned short*)img, dx, g, rp, tiles0, tiles1, tiles2, mask_y, mask_slope, mask_bf16,
                        (float*)nullptr);
   S3_HIP(ctx, hipGetLastError());
+  if (out_bf16) ++ctx->stat[S3_STAT_DGRAD_S2_O16];
+  if (out_bf16 && mask_bits) ++ctx->stat[S3_STAT_DGRAD_S2_MB];
   return S3_OK;
 }

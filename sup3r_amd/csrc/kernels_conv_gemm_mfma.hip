@@ -1030,6 +1030,7 @@ int launch_gconv_fwd(s3_ctx* ctx, const ConvGeom& g, const float* x, const void*
     hipLaunchKernelGGL(kern, hgrid, dim3(FHW * 64), 0, ctx->stream, x, (const unsigned short*)packed, bias, y, g,
                        t0, t1, t2, 0, (unsigned char*)nullptr, x3_fewch_lo_offset(g));
     S3_HIP(ctx, hipGetLastError());
+    ++ctx->stat[S3_STAT_FEWCH_HALO];
     return S3_OK;
   }
   if (fewch_geom(g) && x3) {
@@ -1064,6 +1065,8 @@ int launch_gconv_fwd(s3_ctx* ctx, const ConvGeom& g, const float* x, const void*
       unsigned char* sb = (pm && two && g.Cout == 32) ? (unsigned char*)sign_bytes : nullptr;
       hipLaunchKernelGGL(kern, hgrid, dim3(FHW * 64), 0, ctx->stream, x, img, bias, y, g, t0, t1, t2, out_bf16, sb, 0);
       S3_HIP(ctx, hipGetLastError());
+      ++ctx->stat[S3_STAT_FEWCH_HALO];
+      if (sb) ++ctx->stat[S3_STAT_FEWCH_HALO_SIGNS];
       return S3_OK;
     }
     if (g.Cin == 2)

@@ -411,6 +411,7 @@ int launch_conv_halo_s2_fwd(s3_ctx* ctx, const ConvGeom& g, const void* x, const
                          (const unsigned short*)x, (const unsigned short*)img, bias, (float*)ctx->scratch, y, g,
                          tc.t0, tc.t1, tc.t2, tc.total, out_bf16, ps);
     S3_HIP(ctx, hipGetLastError());
+    ++ctx->stat[S3_STAT_HALO_S2_K64];
     return S3_OK;
   }
   if (int rc = s3_lds_optin(ctx, attr_set,

@@ -137,44 +137,64 @@ def channel_sums(a):
 
 
 # ----------------------------------------------------------------- conv
-def conv_fwd(xp, w, bias=None):
-    """stride-1 'valid' correlation over an already padded input.
-    w: (k0, k1, k2, C_in, C_out)"""
-    k = w.shape[:3]
-    o = [xp.shape[1 + d] - k[d] + 1 for d in range(3)]
-    y = np.zeros((xp.shape[0], o[0], o[1], o[2], w.shape[4]), F64)
+def _strides3(strides, nd=3):
+    """an int (for each of the conv's nd axes) or one stride per axis; the t
+    axis of a 2-D conv has stride 1"""
+    if isinstance(strides, (int, np.integer)):
+        strides = (int(strides),) * nd
+    st = tuple(int(v) for v in strides)
+    return st + (1,) * (3 - len(st))
+
+
+def _taps(xp_shape, k, o, st):
+    """(tap, the slices of the padded input its o outputs read) of a strided
+    'valid' correlation: output i of an axis reads cell i * stride + tap"""
     for a in range(k[0]):
         for b in range(k[1]):
             for c in range(k[2]):
-                y += xp[:, a:a + o[0], b:b + o[1], c:c + o[2], :] @ w[a, b, c]
+                yield (a, b, c), (slice(None),) + tuple(
+                    slice(q, q + (o[d] - 1) * st[d] + 1, st[d]) for d, q in enumerate((a, b, c)))
+
+
+def conv_out(n, k, s=1):
+    """outputs of a 'valid' correlation with stride s over n (padded) cells"""
+    return (n - k) // s + 1
+
+
+def conv_fwd(xp, w, bias=None, strides=1):
+    """'valid' correlation over an already padded input, stride 1 or
+    ``strides`` (an int or per axis).  w: (k0, k1, k2, C_in, C_out)"""
+    k, st = w.shape[:3], _strides3(strides)
+    o = [conv_out(xp.shape[1 + d], k[d], st[d]) for d in range(3)]
+    y = np.zeros((xp.shape[0], o[0], o[1], o[2], w.shape[4]), F64)
+    for tap, sl in _taps(xp.shape, k, o, st):
+        y += xp[sl] @ w[tap]
     return y if bias is None else y + bias
 
 
-def conv_adj_x(dy, w, xp_shape):
-    k = w.shape[:3]
+def conv_adj_x(dy, w, xp_shape, strides=1):
+    k, st = w.shape[:3], _strides3(strides)
     o = dy.shape[1:4]
     dxp = np.zeros(xp_shape, F64)
-    for a in range(k[0]):
-        for b in range(k[1]):
-            for c in range(k[2]):
-                dxp[:, a:a + o[0], b:b + o[1], c:c + o[2], :] += dy @ w[a, b, c].T
+    for tap, sl in _taps(xp_shape, k, o, st):
+        dxp[sl] += dy @ w[tap].T
     return dxp
 
 
-def conv_adj_w(xp, dy, k):
+def conv_adj_w(xp, dy, k, strides=1):
+    st = _strides3(strides)
     o = dy.shape[1:4]
     dw = np.zeros(tuple(k) + (xp.shape[4], dy.shape[4]), F64)
     d2 = dy.reshape(-1, dy.shape[4])
-    for a in range(k[0]):
-        for b in range(k[1]):
-            for c in range(k[2]):
-                xs = xp[:, a:a + o[0], b:b + o[1], c:c + o[2], :]
-                dw[a, b, c] = xs.reshape(-1, xp.shape[4]).T @ d2
+    for tap, sl in _taps(xp.shape, k, o, st):
+        dw[tap] = xp[sl].reshape(-1, xp.shape[4]).T @ d2
     return dw
 
 
-def same_pad(n, k):
-    total = max(k - 1, 0)
+def same_pad(n, k, s=1):
+    """TF 'same': ceil(n / s) outputs; total pad = max((ceil(n / s) - 1) s + k
+    - n, 0), the smaller half in front"""
+    total = max((-(-n // s) - 1) * s + k - n, 0)
     return total // 2, total - total // 2
 
 
@@ -190,7 +210,7 @@ def _pairs(v, nd):
 class RefNet:
     """Eager float64 forward / reverse-mode backward of a ``hidden_layers``
     list restricted to the classes the support-pass tests use: FlexiblePadding,
-    Conv2D / Conv3D (stride 1), LeakyReLU, ReLU, SkipConnection, Cropping2D /
+    Conv2D / Conv3D ('valid' / 'same', any stride), LeakyReLU, ReLU, SkipConnection, Cropping2D /
     3D, SpatialExpansion, SpatioTemporalExpansion (nearest), Sup3rConcat.
     Weights are keras-layout arrays in keras order (kernel, bias per conv)."""
 
@@ -227,12 +247,15 @@ class RefNet:
                     b = self.weights[wi]
                     wi += 1
                 lo = hi = [0, 0, 0]
+                st = _strides3(s.get('strides', 1), self.nd)
                 if s.get('padding', 'valid') == 'same':
-                    sp = [same_pad(x.shape[1 + d], w.shape[d]) for d in range(3)]
+                    sp = [same_pad(x.shape[1 + d], w.shape[d], st[d]) for d in range(3)]
                     lo, hi = [q[0] for q in sp], [q[1] for q in sp]
                 xp = pad_fwd(x, lo, hi, 'constant')
-                tape.append(('conv', x.shape, lo, hi, xp, w, b is not None))
-                x = conv_fwd(xp, w, b)
+                # (a strided conv may leave the last cells of xp unread: they
+                # take no part in either adjoint)
+                tape.append(('conv', x.shape, lo, hi, xp, w, b is not None, st))
+                x = conv_fwd(xp, w, b, st)
             elif cls in ('LeakyReLU', 'ReLU'):
                 slope = float(s.get('alpha', 0.3)) if cls == 'LeakyReLU' else 0.0
                 x = act_fwd(x, slope)
@@ -276,15 +299,15 @@ class RefNet:
             if kind == 'pad':
                 dy = pad_adj(dy, rec[1], rec[2], rec[3], rec[4])
             elif kind == 'conv':
-                _, in_shape, lo, hi, xp, w, has_b = rec
-                g = [conv_adj_w(xp, dy, w.shape[:3])]
+                _, in_shape, lo, hi, xp, w, has_b, st = rec
+                g = [conv_adj_w(xp, dy, w.shape[:3], st)]
                 if self.nd == 2:
                     g[0] = g[0][:, :, 0]
                 if has_b:
                     g.append(channel_sums(dy))
                 grads = g + grads
                 dpre.insert(0, dy)
-                dy = pad_adj(conv_adj_x(dy, w, xp.shape), in_shape, lo, hi,
+                dy = pad_adj(conv_adj_x(dy, w, xp.shape, st), in_shape, lo, hi,
                              'constant')
             elif kind == 'act':
                 dy = act_adj(rec[1], dy, rec[2])

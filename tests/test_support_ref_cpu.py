@@ -160,6 +160,58 @@ def test_conv_and_its_two_adjoints(nd, k, pad):
         assert abs(lhs - rhs) <= 1e-10 * max(1.0, abs(lhs))
 
 
+def test_same_padding_of_a_strided_conv_puts_the_smaller_half_in_front():
+    assert R.same_pad(8, 3, 2) == (0, 1)        # even extent: nothing in front, one zero cell past the end
+    assert R.same_pad(7, 3, 2) == (1, 1)        # odd extent: one cell either side
+    assert R.same_pad(7, 3, 1) == (1, 1) and R.same_pad(7, 1, 2) == (0, 0)
+    assert R.same_pad(6, 2, 3) == (0, 0) and R.same_pad(5, 4, 3) == (1, 1) and R.same_pad(4, 4, 3) == (1, 2)
+    assert [R.conv_out(n, 3, 2) for n in (3, 4, 5, 6)] == [1, 1, 2, 2]
+
+
+STRIDED = [
+    # nd, spatial extents, strides, padding: k = 3, s = 2 on odd and even
+    # extents, both paddings, 2-D and 3-D; one stride per axis
+    (3, (7, 8, 9), 2, 'valid'), (3, (8, 7, 6), 2, 'valid'),
+    (3, (7, 9, 5), 2, 'same'), (3, (8, 6, 10), 2, 'same'), (3, (7, 8, 5), 2, 'same'),
+    (2, (7, 8), 2, 'valid'), (2, (9, 6), 2, 'same'), (2, (8, 7), 2, 'same'),
+    (3, (7, 8, 9), (2, 1, 2), 'same'), (3, (9, 8, 7), (1, 2, 3), 'valid'),
+]
+
+
+@pytest.mark.parametrize('nd,sp,strides,pad', STRIDED)
+def test_strided_conv_and_its_two_adjoints(nd, sp, strides, pad):
+    rng = np.random.default_rng(12)
+    shape = (2,) + sp + (3,)
+    x = rng.standard_normal(shape)
+    layer = OL.ConvND(nd, 4, 3, strides=strides, padding=pad)
+    layer.forward(x)
+    layer.kernel = rng.standard_normal(layer.kernel.shape)
+    layer.bias = rng.standard_normal(layer.bias.shape)
+    y = layer.forward(x)
+    net = R.RefNet([{'class': f'Conv{nd}D', 'filters': 4, 'kernel_size': 3, 'strides': strides, 'padding': pad}], nd)
+    net.set_weights([layer.kernel, layer.bias])
+    y_net = net.forward(x)
+    assert y_net.shape == y.shape
+    _close(y_net, y)
+    dy = rng.standard_normal(y.shape)
+    dx_o = layer.backward(dy)
+    _close(net.backward(dy), dx_o)
+    for a, b in zip(net.grads, layer.grads):
+        _close(a, b)
+    # the tape records the GPU tests read: the padded input and dL / d(conv output)
+    rec = [r for r in net._tape if r[0] == 'conv'][0]
+    st = R._strides3(strides, nd)
+    lo, hi = rec[2], rec[3]
+    assert rec[4].shape[1:4] == tuple(n + a + b for n, a, b in zip(R.to5(x).shape[1:4], lo, hi))
+    np.testing.assert_array_equal(net.dpre[0], R.to5(dy))
+    # ... and the three operations on their own, by the dot-product identities
+    w5, xp = net._kernel5(net.weights[0]), rec[4]
+    _dot_identity(lambda v: R.conv_fwd(v, w5, strides=st), lambda v: R.conv_adj_x(v, w5, xp.shape, st), xp.shape)
+    lhs = float((R.conv_fwd(xp, w5, strides=st) * R.to5(dy)).sum())
+    rhs = float((w5 * R.conv_adj_w(xp, R.to5(dy), w5.shape[:3], st)).sum())
+    assert abs(lhs - rhs) <= 1e-10 * max(1.0, abs(lhs))
+
+
 NETS = [
     # a residual block with reflect convs, a skip tensor with two consumers, a
     # depth-to-space conv, pad / crop
@@ -187,6 +239,16 @@ NETS = [
         {'class': 'Cropping2D', 'cropping': [[1, 0], [2, 1]]},
         {'class': 'FlexiblePadding', 'paddings': [[0, 0], [2, 1], [0, 2], [0, 0]], 'mode': 'CONSTANT'},
         {'class': 'Conv2D', 'filters': 2, 'kernel_size': 1}]),
+    # the discriminator's front: valid / stride-2 / 'same' stride-2 convs chained
+    # (last, so that the ids of the cases above stay what they were)
+    (3, (2, 13, 12, 15, 2), [
+        {'class': 'Conv3D', 'filters': 8, 'kernel_size': 3, 'strides': 1, 'padding': 'valid'},
+        {'class': 'LeakyReLU', 'alpha': 0.25},
+        {'class': 'Conv3D', 'filters': 8, 'kernel_size': 3, 'strides': 2, 'padding': 'valid'},
+        {'class': 'ReLU'},
+        {'class': 'Conv3D', 'filters': 6, 'kernel_size': 3, 'strides': 2, 'padding': 'same'},
+        {'class': 'LeakyReLU', 'alpha': 0.5},
+        {'class': 'Conv3D', 'filters': 4, 'kernel_size': 3, 'strides': 1, 'padding': 'same', 'use_bias': False}]),
 ]
 
 

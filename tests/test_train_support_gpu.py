@@ -104,22 +104,25 @@ def _clean(spec):
     return [{k: v for k, v in s.items() if not k.startswith('_')} for s in spec]
 
 
-def _run(spec, shape, weights, x, d_out, precision='f32', options=None, exo=None, backwards=1):
+def _run(spec, shape, weights, x, d_out, precision='f32', options=None, exo=None, backwards=1, counters=None,
+         need_dx=True):
     """forward + backward(need_dx) of a fresh plan -> (y, dx, grads, counter
-    deltas, op infos).  ``backwards`` > 1: the later passes accumulate."""
+    deltas, op infos).  ``backwards`` > 1: the later passes accumulate.
+    ``counters``: the launch counters to report (default: the support passes')."""
     from sup3r_amd.engine import Network
     net = Network(_clean(spec), precision=precision)
     net.set_weights(weights)
     ph = net.plan(shape, training=True, options=options)
     dev = net.dev
-    before = {k: dev.stat(k) for k in SUPPORT + ('persist_dgrad',)}
+    before = {k: dev.stat(k) for k in (SUPPORT + ('persist_dgrad',) if counters is None else counters)}
     exod = {k: dev.to_device(v) for k, v in (exo or {}).items()}
     y = ph.forward(dev.to_device(x), exod)
     dyd = dev.to_device(d_out)
     for k in range(backwards):
-        dx = ph.backward(dyd, need_dx=True, accumulate_wgrad=k > 0)
+        dx = ph.backward(dyd, need_dx=need_dx, accumulate_wgrad=k > 0)
     dev.sync()
-    y, dx = y.cpu().numpy(), dx.cpu().numpy().reshape(x.shape)   # (dx comes in the plan's 5-D view)
+    y = y.cpu().numpy()
+    dx = dx.cpu().numpy().reshape(x.shape) if need_dx else None   # (dx comes in the plan's 5-D view)
     grads = [g.copy() for g in net.grads]
     used = {k: dev.stat(k) - v for k, v in before.items()}
     info = [ph.op_info(i) for i in range(len(ph.plan.ops)) if ph.plan.ops[i]['kind'] == 1]    # (OP_CONV)
