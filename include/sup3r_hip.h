@@ -886,7 +886,7 @@ int s3_bias_correct(s3_ctx* ctx, const float* x, int n, int s1, int s2, int t, i
  * fp32 once; each output value comes from one thread or from one workgroup's
  * fixed reduction tree; no float atomics.  Index lists come twice: a host copy
  * that is range-checked here before anything is launched, and the device copy
- * that the kernel reads.  All five are asynchronous on the context's stream.
+ * that the kernel reads.  All six are asynchronous on the context's stream.
  *
  * s3_bc_base_series: base (T, n_sites) -> out[p, day_offset + d], d < n_days:
  *   per step the mean over the pixel's sites (CSR site_ptr (P + 1) / site_idx;
@@ -932,6 +932,30 @@ int s3_bias_correct(s3_ctx* ctx, const float* x, int n, int s1, int s2, int t, i
  *   (S3_BCC_PR_STATUS_WORDS int32, zeroed here): non-finite bias values,
  *   non-finite future values, pixels whose round(z_fg Tf) = Tf (the
  *   reference's IndexError; their tau_fut is NaN).  Q >= 2.
+ * s3_bc_skill (SkillAssessment._run_skill_eval, bias_calc.py:431-481), one
+ *   workgroup per pixel over base (P, D) and bias (P, T), D, T <=
+ *   S3_BCC_MAX_SORT.  stats (P, 2, S3_BCC_SK_STATS), series 0 = base, 1 =
+ *   bias: np.nanmean and np.nanstd (two passes in fp64); scipy's biased skew
+ *   m3 / m2^1.5 and Fisher kurtosis m4 / m2^2 - 3 over all n values in fp64
+ *   about the fp64 mean (a NaN in the series gives NaN, and so does m2 <=
+ *   (eps32 mean)^2: scipy's test for a constant float32 series); zero_rate =
+ *   #(x == 0) / n, NaNs counted in n; np.percentile at S3_BCC_SK_PERCENTILES
+ *   = 7 points (1, 5, 25, 50, 75, 95, 99) from the sorted keys, interpolated as
+ *   s3_bc_window_quantiles does at (n - 1) p / 100, NaN where the series holds
+ *   one; and in both rows S3_BCC_SK_BIAS = mean(bias) - mean(base), taken
+ *   between the fp64 means and rounded once (the reference subtracts its two
+ *   float32 means).  status (P, S3_BCC_SK_STATUS_WORDS): NaN and non-finite counts of
+ *   base, then of bias.  ks (P, S3_BCC_SK_KS_WORDS): the two-sample
+ *   Kolmogorov-Smirnov counts, exact: with c1(x) = #(base <= x), c2(x) =
+ *   #(bias <= x) over all data points x (scipy's searchsorted(side='right')),
+ *   (c1, c2) where c1 T - c2 D is largest, then (c1, c2) where it is smallest
+ *   (the smallest c1 among ties; (0, 0) stands for "never below 0").  demean
+ *   != 0: the values compared are x - m32 in fp32, m32 the series' own mean as
+ *   stored in stats; values that the rounding merges tie, and so do -0 and
+ *   +0.  All four words are S3_BCC_SK_NO_KS where either series holds a NaN
+ *   or, with demean, a non-finite value (inf - inf).  sorted_base: (P, D)
+ *   uint32 workspace; the base row's sorted keys rest there while the bias
+ *   row is sorted in LDS (two rows at the limit do not fit together).
  *
  * S3_EINVAL, before anything is launched: a sorted segment longer than
  * S3_BCC_MAX_SORT (its keys fill 128 KiB of the CU's 160 KiB of LDS), a site,
@@ -951,6 +975,18 @@ int s3_bias_correct(s3_ctx* ctx, const float* x, int n, int s1, int s2, int t, i
 #define S3_BCC_PR_BIAS_NONFINITE 0
 #define S3_BCC_PR_FUT_NONFINITE 1
 #define S3_BCC_PR_INDEX 2
+#define S3_BCC_SK_PERCENTILES 7
+#define S3_BCC_SK_STATS 13
+#define S3_BCC_SK_MEAN 0
+#define S3_BCC_SK_STD 1
+#define S3_BCC_SK_SKEW 2
+#define S3_BCC_SK_KURTOSIS 3
+#define S3_BCC_SK_ZERO_RATE 4
+#define S3_BCC_SK_PCT0 5
+#define S3_BCC_SK_BIAS 12
+#define S3_BCC_SK_KS_WORDS 4
+#define S3_BCC_SK_STATUS_WORDS 4
+#define S3_BCC_SK_NO_KS (-1)
 int s3_bc_base_series(s3_ctx* ctx, const float* base, const float* cs_ghi, int64_t T, int64_t n_sites,
                       int P, const int32_t* site_ptr_host, const int32_t* site_idx_host,
                       const int32_t* site_ptr, const int32_t* site_idx, int n_days,
@@ -972,6 +1008,8 @@ int s3_bc_presrat(s3_ctx* ctx, const float* base, int64_t D, const float* bias, 
                   const int32_t* const* member_host, const int32_t* const* win_ptr,
                   const int32_t* const* member, float* corrected, float* zero_rate, float* tau,
                   float* z_fg, float* tau_fut, float* k_factor, int32_t* status);
+int s3_bc_skill(s3_ctx* ctx, const float* base, int64_t D, const float* bias, int64_t T, int P,
+                int demean, uint32_t* sorted_base, float* stats, int32_t* ks, int32_t* status);
 
 /* ---- deriving input features on the device --------------------------------
  * replaces the dask passes of sup3r/preprocessing/derivers (base.py,

@@ -44,7 +44,7 @@ EXPORTS = [
     's3_copy_channels', 's3_affine_channels', 's3_fill', 's3_copy_block',
     's3_coarsen', 's3_gaussian_smooth', 's3_condmom_target', 's3_bias_correct', 's3_chunk_stats',
     's3_bc_base_series', 's3_bc_moments', 's3_bc_window_quantiles',
-    's3_bc_match_zero_rate', 's3_bc_presrat',
+    's3_bc_match_zero_rate', 's3_bc_presrat', 's3_bc_skill',
     's3_sample_gather', 's3_cc_night_mask', 's3_cc_window_gather',
     's3_nn_fill', 's3_channel_moments', 's3_normalize_channels',
     's3_st_interp', 's3_resize2d', 's3_surface_downscale',
@@ -313,6 +313,8 @@ def lib():
                                 vp, vp, vp, i32, C.c_double, vp, vp,
                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                 C.POINTER(vp), vp, vp, vp, vp, vp, vp, vp]),
+        's3_bc_skill': (i32, [vp, vp, i64, vp, i64, i32, i32, vp, vp, vp,
+                              vp]),
         's3_st_interp': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp,
                                vp]),
         's3_resize2d': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp,
@@ -410,6 +412,11 @@ BCC_MAX_SORT, BCC_MAX_GROUPS = 32768, 12
 BCC_AVG, BCC_MAX, BCC_MIN, BCC_SUM, BCC_NONE = range(5)
 BCC_NANSKIP, BCC_CS_RATIO, BCC_ROUND = 1, 2, 4
 BCC_PR_BIAS_NONFINITE, BCC_PR_FUT_NONFINITE, BCC_PR_INDEX = 0, 1, 2
+BCC_SK_PERCENTILES, BCC_SK_STATS = 7, 13
+(BCC_SK_MEAN, BCC_SK_STD, BCC_SK_SKEW, BCC_SK_KURTOSIS, BCC_SK_ZERO_RATE,
+ BCC_SK_PCT0) = range(6)
+BCC_SK_BIAS = 12
+BCC_SK_KS_WORDS, BCC_SK_STATUS_WORDS, BCC_SK_NO_KS = 4, 4, -1
 # s3_level_interp / s3_derive_pointwise / s3_time_flags / s3_stack_features:
 # limits, methods, level sources, ops, modes (include/sup3r_hip.h)
 LI_MAX_LEVELS, LI_MAX_SINGLE, LI_MAX_VARS, LI_MAX_TARGETS = 64, 8, 8, 16

@@ -7,6 +7,7 @@ their own names —
     ScalarCorrection              :256
     MonthlyLinearCorrection       :311
     MonthlyScalarCorrection       :373
+    SkillAssessment               :379
     QuantileDeltaMappingCorrection  qdm.py:35
     PresRat                       presrat.py:42
 
@@ -22,13 +23,15 @@ plain mean, base.py:631); ``base_cs_ghi`` of the same layout for ``base_dset ==
 reference's names and defaults.
 
 The reference gives every low-res pixel to a process pool (abstract.py:79-97);
-here the pixels are workgroups of five kernels (include/sup3r_hip.h):
+here the pixels are workgroups of six kernels (include/sup3r_hip.h):
 
     s3_bc_base_series       site mean + daily reduction -> (P, D)
     s3_bc_match_zero_rate   base.py:557-599
     s3_bc_moments           count, nanmean, nanstd per month
     s3_bc_window_quantiles  np.quantile per day-of-year window
     s3_bc_presrat           corrected future series, zero rate, tau_fut, k_factor
+    s3_bc_skill             moments, zero rate, percentiles and the exact
+                            two-sample KS counts of SkillAssessment
 
 The host plans once per object (numpy / scipy): the KDTree mapping of base
 sites to pixels and its default bound (base.py:175-182, 228-242), the day of
@@ -39,6 +42,9 @@ no window).  ``scalar`` / ``adder`` are formed on the host from the device's
 float32 means and stds with the reference's float32 expressions, and
 ``fill_and_smooth`` (mixins.py:19-102) runs on the host over the finished
 tables with the reference's own scipy calls: they are small and one-off.
+``SkillAssessment``'s KS statistic and p-value are formed on the host from the
+device's integer counts with scipy's own routines (``ks_from_counts``), once
+per distinct numerator.
 
 ``run(fp_out=...)`` writes an ``.npz`` that ``BiasParams.load`` and the five
 transforms of ``sup3r_amd.bias`` read back unchanged.
@@ -56,10 +62,17 @@ Deviations from the reference, on purpose:
   * only ``dist='empirical'`` with ``sampling='linear'``: anything else is a
     ``KeyError``;
   * a sorted series (a window, the bias series of ``match_zero_rate`` and
-    PresRat) holds at most ``BCC_MAX_SORT`` = 32768 values: it is sorted in
-    LDS.  Longer is a ``ValueError``.
+    PresRat, both series of ``SkillAssessment``) holds at most
+    ``BCC_MAX_SORT`` = 32768 values: it is sorted in LDS.  Longer is a
+    ``ValueError``;
+  * ``SkillAssessment`` computes skew and kurtosis in float64 (scipy works in
+    the float32 of its input), takes ``{feat}_bias`` between the float64
+    means and rounds once (the reference subtracts two float32 means), and
+    places its percentiles at the float64 ``(n - 1) p / 100`` (numpy >= 2
+    evaluates that position in float32 for float32 data and a scalar ``p``);
+    its KS test is two-sided only.
 
-Not here: ``SkillAssessment``, ``bias_calc_vortex.py``, the CLIs, reading h5 /
+Not here: ``bias_calc_vortex.py``, the CLIs, reading h5 /
 NetCDF, and deriving u / v from windspeed and direction (the caller passes the
 derived series).
 """
@@ -74,8 +87,8 @@ from . import _lib
 logger = logging.getLogger(__name__)
 
 __all__ = ['LinearCorrection', 'ScalarCorrection', 'MonthlyLinearCorrection',
-           'MonthlyScalarCorrection', 'QuantileDeltaMappingCorrection',
-           'PresRat']
+           'MonthlyScalarCorrection', 'SkillAssessment',
+           'QuantileDeltaMappingCorrection', 'PresRat']
 
 REDUCTIONS = {'avg': _lib.BCC_AVG, 'average': _lib.BCC_AVG,
               'mean': _lib.BCC_AVG, 'max': _lib.BCC_MAX,
@@ -227,6 +240,61 @@ def fill_and_smooth(out, fill_extend=True, smooth_extend=0,
     return out
 
 
+# ----------------------------------------- the KS test from integer counts
+KS_MAX_AUTO_N = 10000      # scipy's ks_2samp(method='auto'): exact up to here
+
+
+def ks_pvalue(n1, n2, h, d):
+    """``ks_2samp(method='auto', alternative='two-sided')`` from where it has
+    its statistic: ``h`` the integer numerator of ``d = h / (n1 n2)`` and
+    ``d`` the float64 statistic.  Returns ``(statistic, pvalue)`` — the exact
+    route re-derives the statistic from ``h`` as scipy does."""
+    import math
+    import warnings
+    from scipy import stats
+    if max(n1, n2) <= KS_MAX_AUTO_N:
+        try:
+            from scipy.stats._stats_py import _attempt_exact_2kssamp
+        except ImportError:                               # a private routine
+            _attempt_exact_2kssamp = None
+        success = False
+        if _attempt_exact_2kssamp is not None:
+            success, d, prob = _attempt_exact_2kssamp(
+                n1, n2, math.gcd(n1, n2), h / (n1 * n2), 'two-sided')
+        if success:
+            return np.float64(d), np.clip(prob, 0, 1)
+        warnings.warn('ks_2samp: Exact calculation unsuccessful. Switching '
+                      'to method=asymp.', RuntimeWarning, stacklevel=2)
+    m, n = sorted([float(n1), float(n2)], reverse=True)
+    prob = stats.distributions.kstwo.sf(d, np.round(m * n / (m + n)))
+    return np.float64(d), np.clip(prob, 0, 1)
+
+
+def ks_from_counts(n1, n2, counts, memo=None):
+    """statistic and p-value of every pixel from the kernel's counts ``(P, 4)``:
+    ``(c1, c2)`` at the largest and at the smallest ``c1 n2 - c2 n1``.  The
+    side is chosen on the integers; the statistic is scipy's float64 ``c1 / n1
+    - c2 / n2``.  ``memo`` (a dict) shares the p-value among the pixels with
+    one numerator and statistic.  Rows of ``BCC_SK_NO_KS`` give NaN."""
+    counts = np.asarray(counts, np.int64)
+    memo = {} if memo is None else memo
+    stat = np.full(len(counts), np.nan)
+    pval = np.full(len(counts), np.nan)
+    for i, (c1p, c2p, c1m, c2m) in enumerate(counts.tolist()):
+        if c1p == _lib.BCC_SK_NO_KS:
+            continue
+        up, down = c1p * n2 - c2p * n1, c2m * n1 - c1m * n2
+        if down > up:
+            h, d = down, np.clip(-(c1m / n1 - c2m / n2), 0, 1)
+        else:
+            h, d = max(up, 0), c1p / n1 - c2p / n2
+        key = (n1, n2, h, float(d))
+        if key not in memo:
+            memo[key] = ks_pvalue(n1, n2, h, d)
+        stat[i], pval[i] = memo[key]
+    return stat, pval
+
+
 # ------------------------------------------------------------ device backend
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
@@ -237,7 +305,7 @@ def _hp(a):
 
 
 class DeviceBackend:
-    """The five kernels behind numpy-in / tensor-out methods.  Series stay on
+    """The six kernels behind numpy-in / tensor-out methods.  Series stay on
     the device between the calls; index lists go up as int32."""
 
     def __init__(self, dev=None):
@@ -349,6 +417,26 @@ class DeviceBackend:
                    int(base_series.shape[1]), self._p(bias_series), n_pix,
                    n_t, self._p(mv), self._p(bad))
         return bias_series, self.to_host(mv), int(self.to_host(bad)[0])
+
+    def skill(self, base_series, bias_series, demean):
+        """host ``dict(stats (P, 2, BCC_SK_STATS) float32 — base, bias —, ks
+        (P, 4) int32, status (P, 4) int32)``"""
+        import torch
+        n_pix, n_d = (int(v) for v in base_series.shape)
+        n_t = int(bias_series.shape[1])
+        if int(bias_series.shape[0]) != n_pix:
+            raise ValueError('base and bias series of different pixel counts')
+        work = self._new((n_pix, max(n_d, 1)), torch.int32)
+        stats = self._new((n_pix, 2, _lib.BCC_SK_STATS), fill=float('nan'))
+        ks = self._new((n_pix, _lib.BCC_SK_KS_WORDS), torch.int32,
+                       _lib.BCC_SK_NO_KS)
+        status = self._new((n_pix, _lib.BCC_SK_STATUS_WORDS), torch.int32, 0)
+        self._call('s3_bc_skill', self._p(base_series), n_d,
+                   self._p(bias_series), n_t, n_pix, int(bool(demean)),
+                   self._p(work), self._p(stats), self._p(ks),
+                   self._p(status))
+        return {'stats': self.to_host(stats), 'ks': self.to_host(ks),
+                'status': self.to_host(status)}
 
     def mask_windows(self, tables, bad_windows):
         """NaN rows for the windows in ``bad_windows`` (host bool ``(W,)``)"""
@@ -628,6 +716,96 @@ class MonthlyScalarCorrection(MonthlyLinearCorrection, ScalarCorrection):
     """bias_calc.py:373-376"""
 
     NT = 12
+
+
+class SkillAssessment(MonthlyLinearCorrection):
+    """bias_calc.py:379-544: the historical skill of one dataset against
+    another — monthly means and stds, and over the whole series the moments,
+    zero rate, seven percentiles and the two-sample KS test of the
+    mean-removed distributions (of the series as they are under
+    ``match_zero_rate``).  As in the reference the ``_scalar`` / ``_adder``
+    tables are created and never written (bias_calc.py:539-542)."""
+
+    PERCENTILES = (1, 5, 25, 50, 75, 95, 99)
+
+    def _init_out(self):
+        feat, dset = self.bias_feature, self.base_dset
+        monthly_keys = [f'{feat}_scalar', f'{feat}_adder',
+                        f'bias_{feat}_mean_monthly',
+                        f'bias_{feat}_std_monthly',
+                        f'base_{dset}_mean_monthly',
+                        f'base_{dset}_std_monthly']
+        annual_keys = [f'{feat}_ks_stat', f'{feat}_ks_p', f'{feat}_bias',
+                       f'bias_{feat}_mean', f'bias_{feat}_std',
+                       f'bias_{feat}_skew', f'bias_{feat}_kurtosis',
+                       f'bias_{feat}_zero_rate', f'base_{dset}_mean',
+                       f'base_{dset}_std', f'base_{dset}_skew',
+                       f'base_{dset}_kurtosis', f'base_{dset}_zero_rate']
+        self.out = {k: np.full((*self.raster_shape, self.NT), np.nan,
+                               np.float32) for k in monthly_keys}
+        for k in annual_keys:
+            self.out[k] = np.full((*self.raster_shape, 1), np.nan, np.float32)
+        for p in self.PERCENTILES:
+            for k in (f'base_{dset}_percentile_{p}',
+                      f'bias_{feat}_percentile_{p}'):
+                self.out[k] = np.full((*self.raster_shape, 1), np.nan,
+                                      np.float32)
+
+    def run(self, fp_out=None, max_workers=None, daily_reduction='avg',
+            fill_extend=True, smooth_extend=0, smooth_interior=0):
+        """bias_calc.py:191-253 over ``_run_single`` (:483-544);
+        ``max_workers`` is accepted and ignored.  ``ks_seconds`` holds the
+        host time spent on the p-values."""
+        import time
+        be = self._backend
+        feat, dset = self.bias_feature, self.base_dset
+        self._init_out()
+        self._check_sort(len(self.bias_ti))
+        base, base_ti = self._base_series(daily_reduction)
+        self._check_sort(len(base_ti))
+        bias = self._bias_series(self.bias_data)
+        if self.match_zero_rate:
+            bias, _, bad = be.match_zero_rate(base, bias)
+            if bad:
+                raise ValueError(f'match_zero_rate: {bad} non-finite values '
+                                 'in bias_data')
+        g_bias, g_base, both = self._groups(self.bias_ti, base_ti)
+        _, bias_mean, bias_std = be.moments(bias, g_bias, self.NT)
+        _, base_mean, base_std = be.moments(base, g_base, self.NT)
+        res = self.get_linear_correction(bias_mean, bias_std, base_mean,
+                                         base_std, feat, dset)
+        for k, v in res.items():
+            if k.endswith(('_scalar', '_adder')):
+                continue
+            v = np.array(v, np.float32)
+            v[:, ~both] = np.nan             # bias_calc.py:532: both or none
+            self.out[k + '_monthly'] = self._good(v)
+        res = be.skill(base, bias, demean=not self.match_zero_rate)
+        good = np.diff(self.site_ptr) > 0
+        tic = time.perf_counter()
+        stat = np.full(self.n_pix, np.nan)
+        pval = np.full(self.n_pix, np.nan)
+        stat[good], pval[good] = ks_from_counts(
+            len(base_ti), len(self.bias_ti), res['ks'][good])
+        self.ks_seconds = time.perf_counter() - tic
+        st = res['stats']
+        tables = {f'{feat}_ks_stat': stat, f'{feat}_ks_p': pval,
+                  f'{feat}_bias': st[:, 1, _lib.BCC_SK_BIAS]}
+        for s, name in ((0, f'base_{dset}'), (1, f'bias_{feat}')):
+            for j, k in ((_lib.BCC_SK_MEAN, 'mean'), (_lib.BCC_SK_STD, 'std'),
+                         (_lib.BCC_SK_SKEW, 'skew'),
+                         (_lib.BCC_SK_KURTOSIS, 'kurtosis'),
+                         (_lib.BCC_SK_ZERO_RATE, 'zero_rate')):
+                tables[f'{name}_{k}'] = st[:, s, j]
+            for j, p in enumerate(self.PERCENTILES):
+                tables[f'{name}_percentile_{p}'] = st[:, s,
+                                                      _lib.BCC_SK_PCT0 + j]
+        for k, v in tables.items():
+            self.out[k] = self._good(np.asarray(v)[:, None])
+        self.out = fill_and_smooth(self.out, fill_extend, smooth_extend,
+                                   smooth_interior)
+        self._write(fp_out, self.out)
+        return copy.deepcopy(self.out)
 
 
 class QuantileDeltaMappingCorrection(_DataRetrievalBase):

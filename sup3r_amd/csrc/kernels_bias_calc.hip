@@ -10,6 +10,9 @@
 //   s3_bc_match_zero_rate   base.py:557-599
 //   s3_bc_presrat           PresRat's corrected future series, zero rate, tau_fut
 //                           and k_factor (presrat.py:96-360)
+//   s3_bc_skill             SkillAssessment's annual part: moments, zero rate,
+//                           percentiles and the two-sample KS counts
+//                           (bias_calc.py:431-481)
 // All series are (P, T), pixel-major.  Sums are fp64 and rounded to fp32 once;
 // every output value is produced by one thread or by one workgroup's fixed
 // reduction tree, so nothing depends on the launch geometry.  No float
@@ -456,6 +459,224 @@ __global__ void __launch_bounds__(kBlk) k_factor_kernel(KFactorArgs a) {
   }
 }
 
+struct SkillArgs {
+  const float* series[2];   // base (P, D), bias (P, T)
+  int n[2];                 // D, T
+  int demean;
+  uint32_t* sorted_base;    // (P, D) workspace: the base row's sorted KS keys
+  float* stats;             // (P, 2, S3_BCC_SK_STATS)
+  int32_t* ks;              // (P, S3_BCC_SK_KS_WORDS)
+  int32_t* status;          // (P, S3_BCC_SK_STATUS_WORDS)
+};
+
+// sum / maximum over the workgroup in a fixed tree (blockDim a power of two);
+// called by the whole workgroup, everyone gets the result
+__device__ double block_sum(double v, double* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+__device__ long long block_max(long long v, long long* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
+    if (tid < s && red[tid + s] > red[tid]) red[tid] = red[tid + s];
+    __syncthreads();
+  }
+  const long long r = red[0];
+  __syncthreads();
+  return r;
+}
+
+// the key that the KS test compares: the value less the series' own fp32 mean
+// (one rounding, as numpy subtracts a float32 scalar from a float32 array),
+// -0 as +0 (compared as floats they tie).  Monotone: sorted keys stay sorted,
+// and values that the rounding merges get one key.
+__device__ __forceinline__ uint32_t ks_key(uint32_t k, float m32, int demean) {
+  float v = key_value(k);
+  if (demean) v = __fsub_rn(v, m32);
+  if (v == 0.f) v = 0.f;
+  return sort_key(v);
+}
+
+// first index in [0, n) whose key is >= b (lower) or > b (upper); n if none
+__device__ __forceinline__ int lower_bound(const uint32_t* keys, int n, uint32_t b) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (keys[mid] < b) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+__device__ __forceinline__ int upper_bound(const uint32_t* keys, int n, uint32_t b) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (keys[mid] <= b) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// bias_calc.py:431-481, one workgroup per pixel.  Per series: the moments in
+// two passes (the second over the keys in LDS), the sort, the percentiles; the
+// base row's sorted KS keys go out to the workspace, the bias row's stay in
+// LDS.  Then the KS counts: with c1(x) = #(base <= x), c2(x) = #(bias <= x)
+// the numerator c1 T - c2 D is evaluated at every data point that can hold an
+// extremum.  c1 is constant between two distinct base values while c2 grows,
+// so on the stretch [b, b_next) the maximum sits at b itself (c1 = the run's
+// end, c2 = upper_bound(bias, b)) and the minimum at the last bias value
+// below b_next (c2 = lower_bound(bias, b_next); where there is none this is
+// the value at b again).  Before the first base value c1 = 0.
+__global__ void __launch_bounds__(kSortBlk) skill_kernel(SkillArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ uint32_t keys[];
+  __shared__ double red[kSortBlk];
+  __shared__ long long redi[kSortBlk];
+  __shared__ int cnt[2][3];                      // per series: NaN, non-finite, zeros
+  const int p = blockIdx.x, tid = threadIdx.x;
+  static constexpr int pct[S3_BCC_SK_PERCENTILES] = {1, 5, 25, 50, 75, 95, 99};
+  if (tid < 6) (&cnt[0][0])[tid] = 0;
+  __syncthreads();
+  double mu_base = 0.0;
+  for (int s = 0; s < 2; ++s) {
+    const int n = a.n[s];
+    const int n2 = pow2_ceil(n);                 // workgroup-uniform
+    const float* x = a.series[s] + (int64_t)p * n;
+    // 1) keys, counts and the sum of what is not NaN
+    double sum = 0.0;
+    int nan = 0, nf = 0, z = 0;
+    for (int i = tid; i < n2; i += blockDim.x) {
+      uint32_t k = kPadKey;
+      if (i < n) {
+        const float v = x[i];
+        k = sort_key(v);
+        if (v != v) ++nan; else sum += (double)v;
+        nf += !(fabsf(v) <= 3.402823466e38f);
+        z += v == 0.f;
+      }
+      keys[i] = k;
+    }
+    if (nan) atomicAdd(&cnt[s][0], nan);
+    if (nf) atomicAdd(&cnt[s][1], nf);
+    if (z) atomicAdd(&cnt[s][2], z);
+    sum = block_sum(sum, red);                   // (its barriers publish keys and counts)
+    const int n_nan = cnt[s][0], n_ok = n - n_nan;
+    const double mu = n_ok ? sum / (double)n_ok : (double)NAN;
+    const float m32 = (float)mu;
+    // 2) central moments about the fp64 mean
+    double s2 = 0.0, s3 = 0.0, s4 = 0.0;
+    for (int i = tid; i < n; i += blockDim.x) {
+      const uint32_t k = keys[i];
+      if (k == kNanKey) continue;
+      const double d = (double)key_value(k) - mu, d2 = d * d;
+      s2 += d2;
+      s3 += d2 * d;
+      s4 += d2 * d2;
+    }
+    s2 = block_sum(s2, red);
+    s3 = block_sum(s3, red);
+    s4 = block_sum(s4, red);
+    bitonic_sort(keys, n2);
+    float* out = a.stats + ((int64_t)p * 2 + s) * S3_BCC_SK_STATS;
+    if (tid < S3_BCC_SK_PERCENTILES) {
+      // np.percentile: window_quantiles_kernel's interpolation at (n - 1) p / 100
+      float v = NAN;
+      if (!n_nan) {
+        const double pos = (double)(n - 1) * ((double)pct[tid] / 100.0);
+        int lo = (int)pos;
+        if (lo > n - 1) lo = n - 1;
+        const double frac = pos - (double)lo;
+        const double va = (double)key_value(keys[lo]);
+        const uint32_t kb = keys[lo + 1 > n - 1 ? lo : lo + 1];
+        if (frac == 0.0 || kb == keys[lo]) {
+          v = (float)va;
+        } else {
+          const double vb = (double)key_value(kb);
+          v = (float)(va + (vb - va) * frac);
+        }
+      }
+      out[S3_BCC_SK_PCT0 + tid] = v;
+    } else if (tid == 64) {                       // (a wave of its own)
+      out[S3_BCC_SK_MEAN] = m32;
+      out[S3_BCC_SK_STD] = n_ok ? (float)sqrt(s2 / (double)n_ok) : NAN;
+      // scipy.stats.skew / kurtosis (biased, Fisher) of float32 data: every
+      // value counts, so a NaN gives NaN; NaN too where m2 <= (eps32 mean)^2
+      float skew = NAN, kurt = NAN;
+      if (!n_nan) {
+        const double m2 = s2 / (double)n, m3 = s3 / (double)n, m4 = s4 / (double)n;
+        const double tiny = 1.1920928955078125e-07 * mu;
+        if (!(m2 <= tiny * tiny)) {
+          skew = (float)(m3 / (m2 * sqrt(m2)));
+          kurt = (float)(m4 / (m2 * m2) - 3.0);
+        }
+      }
+      out[S3_BCC_SK_SKEW] = skew;
+      out[S3_BCC_SK_KURTOSIS] = kurt;
+      out[S3_BCC_SK_ZERO_RATE] = (float)((double)cnt[s][2] / (double)n);
+      if (s == 1) {
+        // the bias of the means from the fp64 means, rounded once
+        const float diff = (float)(mu - mu_base);
+        out[S3_BCC_SK_BIAS] = diff;
+        out[S3_BCC_SK_BIAS - S3_BCC_SK_STATS] = diff;
+      }
+      a.status[(int64_t)p * S3_BCC_SK_STATUS_WORDS + 2 * s] = n_nan;
+      a.status[(int64_t)p * S3_BCC_SK_STATUS_WORDS + 2 * s + 1] = cnt[s][1];
+    }
+    // 3) the KS keys: base out to the workspace, bias in place
+    if (s == 0) {
+      mu_base = mu;
+      uint32_t* ws = a.sorted_base + (int64_t)p * n;
+      for (int i = tid; i < n; i += blockDim.x) ws[i] = ks_key(keys[i], m32, a.demean);
+    } else {
+      __syncthreads();                           // the percentiles have read the keys
+      for (int i = tid; i < n; i += blockDim.x) keys[i] = ks_key(keys[i], m32, a.demean);
+    }
+    __syncthreads();                             // (also makes the workspace row visible to the workgroup)
+  }
+  // 4) the KS counts
+  const int D = a.n[0], T = a.n[1];
+  const uint32_t* ws = a.sorted_base + (int64_t)p * D;
+  constexpr long long kFar = 1ll << 62;
+  long long hi = -kFar, lo = kFar, c1_hi = kFar, c1_lo = kFar;
+  for (int i = tid; i < D; i += blockDim.x) {
+    const uint32_t b = ws[i];
+    const bool last = i == D - 1;
+    const uint32_t bn = last ? 0u : ws[i + 1];
+    if (i == 0) {
+      lo = -(long long)lower_bound(keys, T, b) * D;
+      c1_lo = 0;
+    }
+    if (!last && bn == b) continue;              // not the end of a run of equal keys
+    const long long c1 = i + 1;
+    const long long up = c1 * T - (long long)upper_bound(keys, T, b) * D;
+    const long long dn = c1 * T - (long long)(last ? T : lower_bound(keys, T, bn)) * D;
+    if (up > hi) { hi = up; c1_hi = c1; }
+    const long long m = up < dn ? up : dn;
+    if (m < lo) { lo = m; c1_lo = c1; }
+  }
+  // the extrema, then the smallest c1 that reaches each: c2 follows from both
+  const long long n_hi = block_max(hi, redi);
+  const long long n_lo = -block_max(-lo, redi);
+  const long long w_hi = -block_max(hi == n_hi ? -c1_hi : -kFar, redi);
+  const long long w_lo = -block_max(lo == n_lo ? -c1_lo : -kFar, redi);
+  if (tid == 0) {
+    int32_t* ks = a.ks + (int64_t)p * S3_BCC_SK_KS_WORDS;
+    const bool bad = cnt[0][0] || cnt[1][0] || (a.demean && (cnt[0][1] || cnt[1][1]));
+    ks[0] = bad ? S3_BCC_SK_NO_KS : (int32_t)w_hi;
+    ks[1] = bad ? S3_BCC_SK_NO_KS : (int32_t)((w_hi * T - n_hi) / D);
+    ks[2] = bad ? S3_BCC_SK_NO_KS : (int32_t)w_lo;
+    ks[3] = bad ? S3_BCC_SK_NO_KS : (int32_t)((w_lo * T - n_lo) / D);
+  }
+}
+
 // 0 <= ptr[0] <= ptr[1] <= .. <= ptr[n] == total, every idx in [0, limit)
 bool csr_ok(const int32_t* ptr, int n, const int32_t* idx, int64_t limit) {
   if (ptr[0] != 0) return false;
@@ -471,7 +692,8 @@ int allow_big_lds(s3_ctx* ctx) {
   if (int rc = s3_lds_optin(ctx, attr_set,
                             window_quantiles_kernel, kMaxSort * 4,
                             match_zero_rate_kernel, kMaxSort * 4,
-                            presrat_kernel, kMaxSort * 4)) return rc;
+                            presrat_kernel, kMaxSort * 4,
+                            skill_kernel, kMaxSort * 4)) return rc;
   return S3_OK;
 }
 
@@ -637,6 +859,27 @@ extern "C" int s3_bc_presrat(s3_ctx* ctx, const float* base, int64_t D, const fl
   for (int l = 0; l < 3; ++l) { k.ptr[l] = win_ptr[l]; k.member[l] = member[l]; }
   k.W = W; k.thr = zero_rate_threshold; k.k_factor = k_factor;
   hipLaunchKernelGGL(k_factor_kernel, dim3((unsigned)P), dim3(kBlk), 0, ctx->stream, k);
+  S3_HIP(ctx, hipGetLastError());
+  return S3_OK;
+}
+
+extern "C" int s3_bc_skill(s3_ctx* ctx, const float* base, int64_t D, const float* bias, int64_t T, int P,
+                           int demean, uint32_t* sorted_base, float* stats, int32_t* ks, int32_t* status) {
+  if (!ctx) return S3_EINVAL;
+  if (!base || !bias || !sorted_base || !stats || !ks || !status)
+    S3_FAIL(ctx, S3_EINVAL, "bc_skill: base, bias, the workspace and the three outputs are needed");
+  if (P < 1 || D < 1 || T < 1) S3_FAIL(ctx, S3_EINVAL, "bc_skill: empty extent");
+  if (D > kMaxSort || T > kMaxSort)
+    S3_FAIL(ctx, S3_EINVAL, "bc_skill: a series has more than S3_BCC_MAX_SORT (32768) steps");
+  if ((int64_t)P * D >= kI31 || (int64_t)P * T >= kI31)
+    S3_FAIL(ctx, S3_EINVAL, "bc_skill: 2^31 or more elements");
+  if (int rc = allow_big_lds(ctx)) return rc;
+  SkillArgs a = {};
+  a.series[0] = base; a.series[1] = bias; a.n[0] = (int)D; a.n[1] = (int)T; a.demean = demean != 0;
+  a.sorted_base = sorted_base; a.stats = stats; a.ks = ks; a.status = status;
+  const int n2 = pow2_ceil((int)std::max(D, T));
+  const int blk = n2 > 8192 ? kSortBlk : kBlk;
+  hipLaunchKernelGGL(skill_kernel, dim3((unsigned)P), dim3(blk), (size_t)n2 * 4, ctx->stream, a);
   S3_HIP(ctx, hipGetLastError());
   return S3_OK;
 }
