@@ -1403,6 +1403,73 @@ int s3_site_day_mean(s3_ctx* ctx, const float* src, int64_t t_src, int64_t n_sit
                      float* out);
 int s3_scale_to_time_max(s3_ctx* ctx, const float* a, float* b, int64_t n_pix, int64_t t, float* scale);
 
+/* ---- regridding the low-res member of a dual pair -----------
+ * replaces rex's Regridder as DualRasterizer.update_lr_data calls it
+ * (sup3r/preprocessing/rasterizers/dual.py:187-222): a BallTree over the
+ * source points in the haversine metric, queried with k = 4, inverse-distance
+ * weights, a weighted sum of whole time rows; and the NaN count of
+ * check_regridded_lr_data (:224-249), from the same pass.  The arithmetic is
+ * restated in tests/regrid_ref.py and is UNVERIFIED against rex, which was
+ * not at hand.
+ *
+ * s3_regrid_knn: for each of the n_tgt points tgt (n_tgt, 2) fp32 (lat, lon,
+ * degrees) the k sources (1 <= k <= S3_REGRID_MAX_K) of src (n_src, 2) fp32
+ * with the smallest haversine distance — the exact k nearest, no
+ * approximation.  Arithmetic: the inputs widened to float64 and multiplied by
+ * pi / 180 (numpy's deg2rad), h = sin^2((lat_t - lat_s) / 2) + cos(lat_t)
+ * cos(lat_s) sin^2((lon_t - lon_s) / 2) (scikit-learn's order, h capped at
+ * 1), d = 2 asin(sqrt(h)), nothing contracted.  Candidates are ordered by
+ * (d, source id): the smallest id wins an exact tie (the tree's own choice
+ * follows its traversal: the one documented deviation, as s3_exo_nearest).
+ * idx_out (n_tgt, k) int32, ascending in that order; dist_out (n_tgt, k)
+ * float64 radians, may be NULL; w_out (n_tgt, k) fp32: d32 = float32(d),
+ * floored at 1e-12f, w = 1 / d32, w / (w_0 + w_1 + ... left to right), every
+ * operation a correctly rounded fp32 one.
+ *   The search structure is built by the call, on the device, in work: the
+ * boxes of sources and targets (integer-atomic extrema of order keys; the
+ * host reads these 64 bytes back and lays out the grid, so the call waits for
+ * the stream once), a cell grid over the sources' box with about two sources
+ * per cell, an integer-atomic count per cell, a scan, a scatter of (lat, lon,
+ * cos(lat), id) into cell order.  A target searches square rings of cells
+ * around its own (the border cell it clamps to when it lies outside the box:
+ * such a target is legal and extrapolates from its nearest sources) until its
+ * k-th distance is below min(dlat to the edges of the rectangle searched,
+ * asin(cos(lat_t) sin(dlon to its edges))), less a margin of 2^-20 of the
+ * bound and 1e-12.  The grid has a single longitude cell (latitude bands,
+ * the dlat bound alone) when the longitudes of sources and targets together
+ * span more than 180 degrees or any |lat| exceeds 85 degrees; every candidate
+ * of a cell is measured with the full haversine, so the date line and the
+ * poles are no special case.  The result does not depend on the grid.
+ *
+ * s3_regrid_apply: out[v][j, t] = float32(sum_k float64(w[j, k]) *
+ * float64(src[v][idx[j, k], t])) for t < T_out <= T_src (the reference's crop
+ * lr[..., :T_required], fused), v < n_var; src planes (n_src, T_src), out
+ * planes (n_tgt, T_out), src_planes_host / out_planes_host host arrays of
+ * n_var device pointers (more than 8 variables are split into launches
+ * here).  Every product is exact in fp64; the sum starts from the first
+ * product, runs in rank order k = 0, 1, .. and is rounded to fp32 once, so
+ * the bits depend on nothing else (np.einsum over float32 accumulates in
+ * float32: a documented deviation).  NaN propagates.  nan_count (device,
+ * n_var int64, zeroed here) receives the number of NaN elements written per
+ * variable, one integer atomic per workgroup.  Indices are the library's own:
+ * one outside [0, n_src) is not checked on the device.
+ *
+ * Both use 64-bit element offsets and no float atomics, run on the context's
+ * stream and upload nothing; s3_regrid_apply is asynchronous.  S3_EINVAL,
+ * before anything is launched: n_src or n_tgt outside 1 .. 2^31 - 1, k
+ * outside 1 .. S3_REGRID_MAX_K, n_src < k, a missing or misaligned pointer,
+ * work_bytes below s3_regrid_knn_work_bytes(n_src) (work 8-byte aligned),
+ * n_var < 1, T_out < 1 or T_out > T_src.  A coordinate that is not finite is
+ * S3_EINVAL too, found by the box pass: nothing else has been launched and no
+ * output has been written by then. */
+#define S3_REGRID_MAX_K 8
+int64_t s3_regrid_knn_work_bytes(int64_t n_src);
+int s3_regrid_knn(s3_ctx* ctx, const float* src_lat_lon, int64_t n_src, const float* tgt_lat_lon, int64_t n_tgt,
+                  int k, void* work, int64_t work_bytes, int32_t* idx_out, double* dist_out, float* w_out);
+int s3_regrid_apply(s3_ctx* ctx, int n_var, const float* const* src_planes_host, float* const* out_planes_host,
+                    int64_t n_src, int64_t n_tgt, int64_t T_src, int64_t T_out, int k, const int32_t* idx,
+                    const float* w, int64_t* nan_count);
+
 /* ---- data-parallel gradient sync (RCCL over xGMI) -----------------------
  * replaces: the host-side python sum of per-GPU gradient lists,
  * AbstractSingleModel._sum_parallel_grad (abstract.py:785-805): elementwise

@@ -48,9 +48,11 @@ from . import qa as _qa  # noqa: E402
 from .qa import *  # noqa: E402,F401,F403
 from . import data_handlers as _data_handlers  # noqa: E402
 from .data_handlers import *  # noqa: E402,F401,F403
+from . import dual_rasterizer as _dual_rasterizer  # noqa: E402
+from .dual_rasterizer import *  # noqa: E402,F401,F403
 
 __all__ = ['Sup3rGan', 'Sup3rCondMom', 'Sup3rGanDC', 'SolarCC', 'Sup3rGanWithObs', 'MultiStepGan',
            'MultiStepSurfaceMetGan', 'SolarMultiStepGan', 'LinearInterp', 'SurfaceSpatialMetModel', 'ForwardPass', 'ChunkPathOptions',
            'ChunkSlicer', 'BiasParams', 'DeviceBiasCorrection', 'global_linear_bc', 'local_linear_bc',
            'monthly_local_linear_bc', 'local_qdm_bc', 'local_presrat_bc', 'DeviceBatchQueue', 'DeviceBatchHandler', 'DsetTuple',
-           *_bias_calc.__all__, *_cond.__all__, *_samplers.__all__, *_samplers_cc.__all__, *_dc.__all__, *_dual.__all__, *_derive.__all__, *_exo.__all__, *_stats.__all__, *_qa.__all__, *_data_handlers.__all__, '__version__']
+           *_bias_calc.__all__, *_cond.__all__, *_samplers.__all__, *_samplers_cc.__all__, *_dc.__all__, *_dual.__all__, *_derive.__all__, *_exo.__all__, *_stats.__all__, *_qa.__all__, *_data_handlers.__all__, *_dual_rasterizer.__all__, '__version__']

@@ -62,6 +62,7 @@ EXPORTS = [
     's3_qa_recoarsen', 's3_qa_select', 's3_qa_hist', 's3_qa_power_sum',
     's3_raster_gather', 's3_daily_reduce', 's3_site_day_mean',
     's3_scale_to_time_max',
+    's3_regrid_knn_work_bytes', 's3_regrid_knn', 's3_regrid_apply',
     's3_comm_unique_id', 's3_comm_init', 's3_params_allreduce_grads',
     's3_params_arm_allreduce',
     's3_allreduce_sum', 's3_params_broadcast', 's3_broadcast',
@@ -268,6 +269,11 @@ def lib():
         's3_site_day_mean': (i32, [vp, vp, i64, i64, vp, i64, i32, i64, i32,
                                    vp, i64, vp]),
         's3_scale_to_time_max': (i32, [vp, vp, vp, i64, i64, vp]),
+        's3_regrid_knn_work_bytes': (i64, [i64]),
+        's3_regrid_knn': (i32, [vp, vp, i64, vp, i64, i32, vp, i64, vp, vp,
+                                vp]),
+        's3_regrid_apply': (i32, [vp, i32, C.POINTER(vp), C.POINTER(vp), i64,
+                                  i64, i64, i64, i32, vp, vp, vp]),
         's3_host_register': (i32, [vp, vp, C.c_size_t]),
         's3_host_unregister': (i32, [vp, vp]),
         's3_d2h_window': (i32, [vp, vp, vp, i64, i64, i64, i64, i64, vp]),
@@ -440,6 +446,8 @@ QA_HIST_STATS, QA_HIST_COUNTS, QA_HIST_KEEP_ALL = 1, 2, 4
 RG_GRID, RG_FLAT, RG_FLAT_1D = 0, 1, 2
 DAILY_MAX_SRC, DAILY_MAX_OUT = 8, 16
 DAILY_MEAN, DAILY_MAX, DAILY_MIN, DAILY_SUM, DAILY_RATIO = range(5)
+# s3_regrid_knn / s3_regrid_apply: most neighbours (include/sup3r_hip.h)
+REGRID_MAX_K = 8
 
 
 def last_error(ctx):

@@ -64,9 +64,8 @@ Choices where the reference gave none, and deviations:
 
 Out of scope: reading h5 / NetCDF, ``Cacher`` / ``cache_kwargs``, dask
 chunking; rex's ``get_raster_index`` (``target`` + ``shape`` on flat data
-raises ``NotImplementedError``); ``DualRasterizer`` (rex's ``Regridder``);
-``Sza`` and ``interpolate_na``, which stay ``NotImplementedError``; the k-NN
-query on the device (``scipy.spatial.KDTree`` on the host, as the reference
+raises ``NotImplementedError``); ``Sza`` and ``interpolate_na``, which stay
+``NotImplementedError``; the k-NN query of ``DataHandlerNCforCC`` on the device (``scipy.spatial.KDTree`` on the host, as the reference
 calls it: the targets are a coarse GCM grid); fusing ``coarsen_daily`` into
 the reduction.
 """

@@ -24,7 +24,9 @@ entry points (include/sup3r_hip.h, csrc/kernels_derive.hip):
 
 (and four more for the data handlers, data_handlers.py over
 csrc/kernels_data_handler.hip: ``raster_gather``, ``daily_reduce``,
-``site_day_mean``, ``scale_to_time_max``).
+``site_day_mean``, ``scale_to_time_max``; and two for the dual rasterizer,
+dual_rasterizer.py over csrc/kernels_regrid.hip: ``regrid_knn``,
+``regrid_apply``).
 ``NumpyBackend`` is the same arithmetic restated in numpy, for testing the
 host control flow on a machine without a GPU; it is no fallback: nothing
 selects it but the caller.
@@ -433,6 +435,77 @@ class NumpyBackend:
                 np.float32)
             return (b * scale[..., None]).astype(np.float32), scale
 
+    # -- the regridder's operations (dual_rasterizer.py)
+    def regrid_knn(self, src_lat_lon, tgt_lat_lon, k):
+        """the ``k`` nearest of the sources ``(n_src, 2)`` (lat, lon, degrees)
+        for every target ``(n_tgt, 2)``, by the device's rules
+        (``s3_regrid_knn``): float32 inputs widened to float64, the haversine
+        distance in radians by brute force, candidates in ``(distance, id)``
+        order, rex's float32 inverse-distance weights.  Returns the handle
+        ``regrid_apply`` takes: ``idx`` int32, ``dist`` float64 and ``w``
+        float32, all ``(n_tgt, k)``."""
+        src = np.deg2rad(np.asarray(src_lat_lon, np.float32).reshape(-1, 2)
+                         .astype(np.float64))
+        tgt = np.deg2rad(np.asarray(tgt_lat_lon, np.float32).reshape(-1, 2)
+                         .astype(np.float64))
+        n, m, k = len(src), len(tgt), int(k)
+        if not 1 <= k <= _lib.REGRID_MAX_K or n < k or m < 1:
+            raise ValueError(f'regrid_knn: k = {k} with {n} sources and {m} '
+                             f'targets (1 <= k <= {_lib.REGRID_MAX_K}, '
+                             'k <= n_src, 1 <= n_tgt)')
+        if not (np.isfinite(src).all() and np.isfinite(tgt).all()):
+            raise ValueError('regrid_knn: a coordinate that is not finite')
+        cos_s = np.cos(src[:, 0])
+        idx = np.empty((m, k), np.int32)
+        dist = np.empty((m, k), np.float64)
+        step = max(1, (1 << 21) // n)
+        for at in range(0, m, step):
+            t = tgt[at:at + step]
+            s0 = np.sin(0.5 * (t[:, None, 0] - src[None, :, 0]))
+            s1 = np.sin(0.5 * (t[:, None, 1] - src[None, :, 1]))
+            h = s0 * s0 + np.cos(t[:, None, 0]) * cos_s[None] * s1 * s1
+            d = 2.0 * np.arcsin(np.sqrt(np.minimum(h, 1.0)))
+            # stable: equal distances stay in id order
+            first = np.argsort(d, axis=1, kind='stable')[:, :k]
+            idx[at:at + step] = first
+            dist[at:at + step] = np.take_along_axis(d, first, axis=1)
+        return {'idx': idx, 'dist': dist, 'w': self.regrid_weights(dist),
+                'n_src': n, 'n_tgt': m, 'k': k}
+
+    @staticmethod
+    def regrid_weights(dist):
+        """rex's weights: float32 distances floored at 1e-12, their
+        reciprocals, divided by their sum taken left to right"""
+        d = np.asarray(dist).astype(np.float32)
+        d[d < np.float32(1e-12)] = np.float32(1e-12)
+        w = np.float32(1.0) / d
+        total = w[:, 0].copy()
+        for q in range(1, w.shape[1]):
+            total = total + w[:, q]
+        return (w / total[:, None]).astype(np.float32)
+
+    def regrid_apply(self, handle, planes, t_out):
+        """``out[j, t] = float32(sum_k float64(w[j, k]) float64(plane[idx[j,
+        k], t]))`` for ``t < t_out``, the sum in rank order from the first
+        product (``s3_regrid_apply``); planes ``(s1, s2, T)`` or ``(n_src,
+        T)``.  Returns ``(planes (n_tgt, t_out), NaN count of each)``."""
+        idx, w = handle['idx'].astype(np.int64), handle['w'].astype(np.float64)
+        outs, counts = [], []
+        with np.errstate(all='ignore'):
+            for a in planes:
+                a = np.asarray(a, np.float32)
+                rows = a.reshape(handle['n_src'], a.shape[-1])
+                if not 1 <= t_out <= rows.shape[1]:
+                    raise ValueError('regrid_apply: 1 <= t_out <= T is needed')
+                rows = rows[:, :t_out]
+                acc = w[:, 0, None] * rows[idx[:, 0]].astype(np.float64)
+                for q in range(1, handle['k']):
+                    acc = acc + w[:, q, None] * rows[idx[:, q]].astype(
+                        np.float64)
+                outs.append(acc.astype(np.float32))
+                counts.append(int(np.isnan(outs[-1]).sum()))
+        return outs, np.asarray(counts, np.int64)
+
     def to_index(self, x):
         return np.ascontiguousarray(x, dtype=np.int32)
 
@@ -746,6 +819,46 @@ class DeviceBackend:
         self._call('s3_scale_to_time_max', _ptr(a), _ptr(b), s1 * s2, t,
                    _ptr(scale))
         return b, scale
+
+    # -- the regridder's kernels (csrc/kernels_regrid.hip)
+    def regrid_knn(self, src_lat_lon, tgt_lat_lon, k):
+        """as ``NumpyBackend.regrid_knn`` (``s3_regrid_knn``); the handle's
+        tables stay on the device"""
+        import torch
+        td = self.dev.torch_device
+        src = self.asarray(np.ascontiguousarray(
+            np.asarray(src_lat_lon, np.float32).reshape(-1, 2)))
+        tgt = self.asarray(np.ascontiguousarray(
+            np.asarray(tgt_lat_lon, np.float32).reshape(-1, 2)))
+        n, m, k = int(src.shape[0]), int(tgt.shape[0]), int(k)
+        n_bytes = int(_lib.lib().s3_regrid_knn_work_bytes(n))
+        if n_bytes < 0:
+            raise ValueError('s3_regrid_knn: 1 .. 2^31 - 1 sources')
+        work = torch.empty((n_bytes + 7) // 8, dtype=torch.int64, device=td)
+        idx = torch.empty((m, max(k, 1)), dtype=torch.int32, device=td)
+        dist = torch.empty((m, max(k, 1)), dtype=torch.float64, device=td)
+        w = torch.empty((m, max(k, 1)), dtype=torch.float32, device=td)
+        self._call('s3_regrid_knn', _ptr(src), n, _ptr(tgt), m, k, _ptr(work),
+                   work.numel() * 8, _ptr(idx), _ptr(dist), _ptr(w))
+        return {'idx': idx, 'dist': dist, 'w': w, 'n_src': n, 'n_tgt': m,
+                'k': k}
+
+    def regrid_apply(self, handle, planes, t_out):
+        """as ``NumpyBackend.regrid_apply``: all planes in one call
+        (``s3_regrid_apply``); the NaN counts stay on the device (int64)"""
+        import torch
+        planes = [a.contiguous() for a in planes]
+        n, m = handle['n_src'], handle['n_tgt']
+        t_src = int(planes[0].shape[-1])
+        for a in planes:
+            assert a.numel() == n * t_src, (tuple(a.shape), n, t_src)
+        outs = [self.dev.empty((m, max(int(t_out), 1))) for _ in planes]
+        counts = torch.empty(len(planes), dtype=torch.int64,
+                             device=self.dev.torch_device)
+        self._call('s3_regrid_apply', len(planes), self._pointers(planes),
+                   self._pointers(outs), n, m, t_src, int(t_out), handle['k'],
+                   _ptr(handle['idx']), _ptr(handle['w']), _ptr(counts))
+        return outs, counts
 
 # --------------------------------------------------------------- the dataset
 class DeriveData:
