@@ -131,7 +131,16 @@ enum { S3_STAT_PERSIST_DGRAD = 0, /* trunk data gradients on the persistent kern
        S3_STAT_FEWCH_HALO_SIGNS = 30, /* ... of those, the ones that wrote activation sign bytes   */
        S3_STAT_DGRAD_S2_O16 = 31,   /* stride-2 data gradients that stored dx as bf16 only        */
        S3_STAT_DGRAD_S2_MB = 32,    /* ... of those, the ones that masked from sign bytes         */
-       S3_STAT_COUNT = 33 };
+       /* variants of the hi-res tail conv: s3_plan_op_info reports tail_mfma / tail for all of them */
+       S3_STAT_TAIL_TILE = 33,      /* forward: conv_tail_mfma_kernel<false> (4 x 8 x 64 tiles)   */
+       S3_STAT_TAIL_BAND = 34,      /* forward: conv_tail_mfma_kernel<true> (banded rows, C_out 2) */
+       S3_STAT_TAIL_SLIDE = 35,     /* forward: conv_tail_slide_kernel (16 x 64 column along s0)  */
+       S3_STAT_TAIL_SWEEP = 36,     /* forward: conv_tail_sweep_kernel (plane sweep)              */
+       S3_STAT_TAIL_X3 = 37,        /* forward: conv_tail_x3_kernel (split bf16)                  */
+       S3_STAT_WGRAD_TAIL_TILE = 38,      /* weight gradient: conv_wgrad_tail_kernel<false> (fp32 cells) */
+       S3_STAT_WGRAD_TAIL_TILE_IN16 = 39, /* weight gradient: conv_wgrad_tail_kernel<true> (bf16 cells)  */
+       S3_STAT_WGRAD_TAIL_SWEEP = 40,     /* weight gradient: conv_wgrad_tail_sweep_kernel               */
+       S3_STAT_COUNT = 41 };
 int64_t s3_ctx_stat(const s3_ctx* ctx, int which);
 
 /* ---- parameter store ---------------------------------------------------

@@ -361,7 +361,11 @@ STATS = {'persist_dgrad': 0, 'gconv_splitk': 1, 'bucket_elems': 2,
          'persist_skippre': 27,
          # in-family variants of the discriminator's conv kernels
          'halo_s2_k64': 28, 'fewch_halo': 29, 'fewch_halo_signs': 30,
-         'dgrad_s2_o16': 31, 'dgrad_s2_mb': 32}
+         'dgrad_s2_o16': 31, 'dgrad_s2_mb': 32,
+         # variants of the hi-res tail conv, forward and weight gradient
+         'tail_tile': 33, 'tail_band': 34, 'tail_slide': 35, 'tail_sweep': 36,
+         'tail_x3': 37, 'wgrad_tail_tile': 38, 'wgrad_tail_tile_in16': 39,
+         'wgrad_tail_sweep': 40}
 
 
 def option_names():

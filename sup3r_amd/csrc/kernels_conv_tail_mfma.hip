@@ -565,6 +565,7 @@ int launch_conv_tail_mfma(s3_ctx* ctx, const ConvGeom& g, const void* x,
     hipLaunchKernelGGL(conv_tail_slide_kernel, dim3(sgrid), dim3(NTH), SLIDE_LDS, ctx->stream,
                        (const unsigned short*)x, w, bias, y, g, segs0, st1, st2, n_units, seg, aff);
     S3_HIP(ctx, hipGetLastError());
+    ++ctx->stat[S3_STAT_TAIL_SLIDE];
     return S3_OK;
   }
   const int grid = persistent_grid(ctx->num_cu, tc.total);
@@ -572,5 +573,6 @@ int launch_conv_tail_mfma(s3_ctx* ctx, const ConvGeom& g, const void* x,
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NTH), 2 * BUF_BYTES, ctx->stream,
                      (const unsigned short*)x, w, bias, y, g, tc.t0, tc.t1, tc.t2, tc.total, aff);
   S3_HIP(ctx, hipGetLastError());
+  ++ctx->stat[band ? S3_STAT_TAIL_BAND : S3_STAT_TAIL_TILE];
   return S3_OK;
 }

@@ -323,5 +323,6 @@ int launch_conv_tail_sweep(s3_ctx* ctx, const ConvGeom& g, const void* x, const 
   hipLaunchKernelGGL(kern, dim3(grid), dim3(SW_NTH), SW_NSLOT * sh.plane_bytes, ctx->stream,
                      (const unsigned short*)x, w, bias, y, g, sh, aff);
   S3_HIP(ctx, hipGetLastError());
+  ++ctx->stat[S3_STAT_TAIL_SWEEP];
   return S3_OK;
 }

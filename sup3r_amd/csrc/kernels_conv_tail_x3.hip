@@ -193,5 +193,6 @@ int launch_conv_tail_x3(s3_ctx* ctx, const ConvGeom& g, const float* x, const fl
   hipLaunchKernelGGL(conv_tail_x3_kernel, dim3(8 * per_xcd), dim3(XNT), XLDS, ctx->stream, x, w, bias, y, g,
                      tiles0, tiles1, tiles2, n_tiles, per_xcd);
   S3_HIP(ctx, hipGetLastError());
+  ++ctx->stat[S3_STAT_TAIL_X3];
   return S3_OK;
 }

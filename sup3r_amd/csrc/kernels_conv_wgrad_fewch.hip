@@ -1108,6 +1108,7 @@ int launch_conv_wgrad_tail(s3_ctx* ctx, const ConvGeom& g, const float* x, const
     hipLaunchKernelGGL(wgrad_c2_partial_reduce, dim3((wsz + 15) / 16), dim3(256), 0, ctx->stream,
                        partial, sgrid, wsz, dw, accumulate);
     S3_HIP(ctx, hipGetLastError());
+    ++ctx->stat[S3_STAT_WGRAD_TAIL_SWEEP];
     return S3_OK;
   }
   static S3DeviceOnce attr_set;
@@ -1125,5 +1126,6 @@ int launch_conv_wgrad_tail(s3_ctx* ctx, const ConvGeom& g, const float* x, const
   hipLaunchKernelGGL(wgrad_c2_partial_reduce, dim3((wsize + 15) / 16), dim3(256), 0, ctx->stream,
                      partial, grid, wsize, dw, accumulate);
   S3_HIP(ctx, hipGetLastError());
+  ++ctx->stat[x_bf16 ? S3_STAT_WGRAD_TAIL_TILE_IN16 : S3_STAT_WGRAD_TAIL_TILE];
   return S3_OK;
 }

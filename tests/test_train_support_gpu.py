@@ -69,7 +69,8 @@ def _weights(spec, cin, rng, nd, kind='one_hot', bias=True):
     """keras-order weights: one +-1 per output channel (``one_hot``: any (tap,
     input channel); ``perm``: C_in == C_out, every input channel fed by exactly
     one (tap, output channel); ``inj``: no (tap, input channel) feeds two
-    output channels) or the identity (1 x 1 convs), integer biases"""
+    output channels), +-1 in EVERY entry (``dense``) or the identity (1 x 1
+    convs), integer biases"""
     out = []
     for s in spec:
         if s['class'] not in ('Conv2D', 'Conv3D'):
@@ -89,6 +90,8 @@ def _weights(spec, cin, rng, nd, kind='one_hot', bias=True):
         elif mode == 'inj':
             slot = rng.choice(taps * cin, size=cout, replace=False)
             flat[slot // cin, slot % cin, np.arange(cout)] = rng.choice([-1.0, 1.0], size=cout)
+        elif mode == 'dense':
+            flat[:] = rng.choice([-1.0, 1.0], size=flat.shape)
         else:
             src = rng.permutation(cin) if mode == 'perm' else rng.integers(cin, size=cout)
             flat[rng.integers(taps, size=cout), src, np.arange(cout)] = rng.choice([-1.0, 1.0], size=cout)
